@@ -14,6 +14,11 @@ of the window, as Lattice::Iterate does).  Compute and storage precision: fp64
 (the reference default, src/configure.ac:208-211) unless --precision names one of the
 reduced-storage modes (mixed[-shift]: fp64 compute / fp32 storage, half[-shift]: fp32
 compute / fp16 storage; *-shift stores f - w_i, reference --with-storage=...-shift).
+
+A plain run sets up, warms up, times the window and prints the result line.  --full adds
+what the headline figure does not need: the physics checks (mass conservation, x/z
+invariance, the collision guard; exit 3 when one fails) and the host enqueue cost of a
+step.  --dump-outputs DIR writes what the last timed step left (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -106,6 +111,52 @@ def physics_checks(lat: Lattice, comm, mass0: float, precision: str) -> dict:
             "z_invariant": zinv, "x_invariant": xinv, "collides": coll, "collision_rel_diff": g["rel_diff"]}
 
 
+DUMP_SEED = 27512          # the node sample of --dump-outputs: the same nodes in every run
+DUMP_NODES = 65536
+
+
+def fields_at(lat: Lattice, comm, x: np.ndarray, y: np.ndarray, z: np.ndarray):
+    """every field at the global nodes (x[i], y[i], z[i]) as (nf, n) float64, the storage
+    shift of the *-shift modes added back; each rank reads the nodes of its own block, the
+    whole array is returned on rank 0 (None elsewhere)"""
+    nx, ny, nz = lat.shape
+    _, oy, oz = lat.slab.offset
+    mine = np.nonzero((y >= oy) & (y < oy + ny) & (z >= oz) & (z < oz + nz))[0]
+    ix, iy, iz = (torch.as_tensor(v[mine] + o, dtype=torch.int64, device=lat.device)
+                  for v, o in ((x, 0), (y, lat.gy - oy), (z, lat.gz - oz)))
+    v = lat.snaps[lat.cur][:, iz, iy, ix].to(torch.float64)
+    if lat._shift_t is not None:
+        v = v + lat._shift_t.view(-1, 1)
+    parts = comm.gather_to_root((mine, v.cpu().numpy()))
+    if parts is None:
+        return None
+    out = np.zeros((lat.nf, len(x)), dtype=np.float64)
+    for idx, val in parts:
+        out[:, idx] = val
+    return out
+
+
+def dump_outputs(lat: Lattice, comm, dirname: str):
+    """what a caller of the timed path holds after its last step, as DIR/<name>.npy (float64):
+    globals         (NG,) the globals the last step integrated, in the model's order
+    fields_sample   (nf, DUMP_NODES) every stored field at a fixed, seeded sample of the
+                    global lattice's nodes (the whole 512^3 state is 29 GB)
+    fields_profile_y (nf, ny) every stored field along y at x = nx/2, z = nz/2 (wall to wall)
+    The sample depends on the global shape alone, not on the rank count."""
+    gnx, gny, gnz = lat.gshape
+    rng = np.random.default_rng(DUMP_SEED)
+    flat = rng.integers(0, gnx * gny * gnz, size=DUMP_NODES, dtype=np.int64)
+    sample = fields_at(lat, comm, flat % gnx, (flat // gnx) % gny, flat // (gnx * gny))
+    yy = np.arange(gny, dtype=np.int64)
+    profile = fields_at(lat, comm, np.full_like(yy, gnx // 2), yy, np.full_like(yy, gnz // 2))
+    if comm.rank == 0:
+        os.makedirs(dirname, exist_ok=True)
+        glob = np.array([lat.globals[g.name] for g in lat.model.globals_], dtype=np.float64)
+        np.save(os.path.join(dirname, "globals.npy"), glob)
+        np.save(os.path.join(dirname, "fields_sample.npy"), sample)
+        np.save(os.path.join(dirname, "fields_profile_y.npy"), profile)
+
+
 def main():
     argv = sys.argv[1:]
     ap = argparse.ArgumentParser()
@@ -128,6 +179,12 @@ def main():
                     help="halo transport of --loopback-dist (rccl: RCCL send/receive to itself)")
     ap.add_argument("--python-loop", action="store_true",
                     help="multi-rank steps from the Python step path instead of the native loop (A/B)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the physics checks (exit 3 when one fails) and measure the host "
+                         "enqueue cost of a step; a plain run only times the window")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's globals and a fixed sample of "
+                         "its fields as DIR/<name>.npy")
     a = ap.parse_args()
     ws = int(os.environ.get("WORLD_SIZE", "0") or 0)
     if ws == 0 and a.gpus is not None and a.gpus > 1:
@@ -163,7 +220,7 @@ def main():
     lat.set_setting("nu", 0.02)
     lat.set_setting("ForceX", 1e-6)
     lat.init()
-    mass0 = total_mass(lat, comm)
+    mass0 = total_mass(lat, comm) if a.full else None
 
     def sync():
         if use_gpu:
@@ -176,12 +233,14 @@ def main():
         # wait in the barrier below; the launcher must end the job, not hang
         raise SystemExit(f"bench.py: rank {rank} failing on purpose (TCLB_BENCH_FAIL_RANK)")
     sync()
-    # host cost of a step on an idle queue: the enqueue time of a few steps (launches,
-    # events, RCCL group calls) before the GPU has caught up — outside the timed window
-    th = time.perf_counter()
-    lat.iterate(4, glob_last=False)
-    t_enqueue = (time.perf_counter() - th) / 4
-    sync()
+    t_enqueue = None
+    if a.full:
+        # host cost of a step on an idle queue: the enqueue time of a few steps (launches,
+        # events, RCCL group calls) before the GPU has caught up — outside the timed window
+        th = time.perf_counter()
+        lat.iterate(4, glob_last=False)
+        t_enqueue = (time.perf_counter() - th) / 4
+        sync()
     it0 = lat.iter
     t0 = time.perf_counter()
     if a.glob_every_step:
@@ -204,8 +263,16 @@ def main():
     t_host = comm.allreduce_scalar(t_host, "max")
     nodes = shape[0] * shape[1] * shape[2]
     mlups = nodes * a.steps / dt / 1e6
-    chk = physics_checks(lat, comm, mass0, a.precision)
-    ok = chk["globals_finite"] and chk["mass_ok"] and chk["z_invariant"] and chk["x_invariant"] and chk["collides"]
+    if a.dump_outputs:
+        dump_outputs(lat, comm, a.dump_outputs)
+    if a.full:
+        chk = physics_checks(lat, comm, mass0, a.precision)
+        ok = chk["globals_finite"] and chk["mass_ok"] and chk["z_invariant"] and chk["x_invariant"] and chk["collides"]
+    else:
+        # the globals of the last timed step are at hand; the checks that step the lattice
+        # again or read all of it are --full's
+        ok = all(np.isfinite(v) for v in lat.globals.values())
+        chk = {"globals_finite": ok}
     if rank == 0:
         es = lat.snaps[0].element_size()
         nf = lat.nf
@@ -236,7 +303,8 @@ def main():
             "tile_split": lat.tile_split,
             "placement": lat.placement,
             "host_ms_per_step": round(t_host / max(1, a.steps - 1) * 1e3, 4) if not a.glob_every_step else None,
-            "host_enqueue_ms_per_step": round(t_enqueue * 1e3, 4),
+            "host_enqueue_ms_per_step": round(t_enqueue * 1e3, 4) if t_enqueue is not None else None,
+            "full": a.full,
             "loop": ("native-dist/" + lat._dist.transport) if (lat._dist is not None and lat.comm.distributed) else
                     {"lib": "native", "loop": "native-loop", None: "python"}[lat._native_path("Iteration")],
             "baseline_note": "reference publishes no MLUPS (BASELINE.md); vs_baseline null",

@@ -1,12 +1,12 @@
 #!/bin/bash
-# RCCL self-send on a slab against the channel count: physics checks of bench.py decide
+# RCCL self-send on a slab against the channel count: physics checks of bench.py --full decide
 # (rc 3 = a check failed; rc >= 124 or a signal: stop)
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/${TAG:-rcclch}; mkdir -p $O; cd $R
 run() {  # name, env..., -- bench args
   local name=$1; shift
   local envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
   echo "== $name"
-  timeout -k 10 300 env "${envs[@]}" python bench.py "$@" > $O/$name.json 2> $O/$name.err
+  timeout -k 10 300 env "${envs[@]}" python bench.py --full "$@" > $O/$name.json 2> $O/$name.err
   local rc=$?
   tail -c 300 $O/$name.json; grep -h "physics check" $O/$name.err | cut -c1-300
   echo "   rc=$rc"

@@ -14,7 +14,7 @@ def _run(nproc, port):
     env = dict(os.environ, PYTHONPATH=ROOT, OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--cpu", "--shape", "32,16,16", "--steps", "3", "--warmup", "1", "--gpus", str(nproc)]
+           "--cpu", "--shape", "32,16,16", "--steps", "3", "--warmup", "1", "--gpus", str(nproc), "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -42,7 +42,7 @@ def test_bench_eight_ranks_like_the_scaling_run():
     env = dict(os.environ, PYTHONPATH=ROOT, OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8",
            "--master-addr", "127.0.0.1", "--master-port", "29617", os.path.join(ROOT, "bench.py"),
-           "--cpu", "--size", "32", "--steps", "3", "--warmup", "1", "--gpus", "8"]
+           "--cpu", "--size", "32", "--steps", "3", "--warmup", "1", "--gpus", "8", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -60,7 +60,7 @@ def test_bench_spawns_its_own_ranks():
     env = dict(os.environ, PYTHONPATH=ROOT, OMP_NUM_THREADS="2")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--cpu", "--gpus", "2", "--shape", "32,16,16",
-           "--steps", "3", "--warmup", "1"]
+           "--steps", "3", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -94,6 +94,64 @@ def test_bench_window_holds_exactly_steps_iterations():
         assert out["iterations_timed"] == steps and out["steps"] == steps
         window = 32 * 16 * 16 * steps / (out["value"] * 1e6)          # seconds, from the MLUPS
         assert abs(out["ms_per_step"] * steps / 1e3 - window) <= 0.01 * window + 1e-7
+
+
+def test_bench_plain_run_dumps_repeatable_outputs(tmp_path):
+    """a plain run (no --full) times the window only — no physics checks, no enqueue probe —
+    and --dump-outputs writes the last step's globals and field sample as float64 .npy, the
+    same from run to run"""
+    import numpy as np
+    env = dict(os.environ, PYTHONPATH=ROOT, OMP_NUM_THREADS="2")
+    env.pop("WORLD_SIZE", None)
+    dumps = []
+    for rep in ("a", "b"):
+        d = str(tmp_path / rep)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--cpu", "--gpus", "1", "--shape", "32,16,16",
+               "--steps", "3", "--warmup", "1", "--dump-outputs", d]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["full"] is False and out["iterations_timed"] == 3 and out["ms_per_step"] > 0
+        assert out["checks"] == {"globals_finite": True} and out["host_enqueue_ms_per_step"] is None
+        assert sorted(os.listdir(d)) == ["fields_profile_y.npy", "fields_sample.npy", "globals.npy"]
+        dumps.append({f: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+    a, b = dumps
+    assert a["fields_sample.npy"].shape == (27, 65536) and a["fields_profile_y.npy"].shape == (27, 16)
+    for f in a:
+        assert a[f].dtype == np.float64 and np.isfinite(a[f]).all()
+    assert np.array_equal(a["fields_sample.npy"], b["fields_sample.npy"])
+    assert np.array_equal(a["fields_profile_y.npy"], b["fields_profile_y.npy"])
+    # the globals are summed by OpenMP threads / GPU atomics: equal to rounding
+    np.testing.assert_allclose(a["globals.npy"], b["globals.npy"], rtol=1e-12, atol=1e-300)
+
+
+def test_dump_outputs_holds_the_lattice_state(tmp_path):
+    """dump_outputs against the lattice it was taken from: the sampled nodes and the y line
+    equal fields_interior (storage shift added back), the globals the lattice's"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from tclb_amd.lattice import Lattice
+    for precision in ("double", "mixed-shift"):
+        lat = Lattice("d3q27", (24, 10, 6), device=torch.device("cpu"), precision=precision)
+        lat.set_flags(bench.channel_flags(lat))
+        lat.set_setting("nu", 0.02)
+        lat.set_setting("ForceX", 1e-4)
+        lat.init()
+        lat.iterate(3)
+        d = str(tmp_path / precision)
+        bench.dump_outputs(lat, lat.comm, d)
+        ref = lat.fields_interior(torch.float64).numpy()          # (nf, nz, ny, nx)
+        flat = np.random.default_rng(bench.DUMP_SEED).integers(0, 24 * 10 * 6, size=bench.DUMP_NODES, dtype=np.int64)
+        assert len(np.unique(flat)) == 24 * 10 * 6               # every node of this small lattice
+        assert np.array_equal(np.load(os.path.join(d, "fields_sample.npy")), ref.reshape(27, -1)[:, flat])
+        assert np.array_equal(np.load(os.path.join(d, "fields_profile_y.npy")), ref[:, 3, :, 12])
+        g = np.load(os.path.join(d, "globals.npy"))
+        assert g.tolist() == [lat.globals[gl.name] for gl in lat.model.globals_]
+        assert np.ptp(ref[0, 3, :, 12]) > 0                      # the profile is not flat: walls + force
 
 
 def test_bench_rank_failure_ends_the_job():
