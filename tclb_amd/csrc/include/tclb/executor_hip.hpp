@@ -216,37 +216,25 @@ __device__ __forceinline__ uint3 list_tile(const Launch& L, const unsigned* list
   return make_uint3(b % gx, (b / gx) % gy, b / (gx * gy));
 }
 
-// Occupancy floor of every stage kernel (build variant "sw2", -DTCLB_STAGE_WAVES=W): a
-// kernel just past 256 VGPRs runs at 1 wave/SIMD; the cap trades that for spills (A/B of
-// the register-heavy collisions, e.g. the tePSM CHT collide).  0 = no cap (default).
+// ---------------------------------------------------------------- occupancy floors
+// The amdgpu_waves_per_eu value of every stage kernel comes from stage_waves() below (0: no
+// floor).  TCLB_SPLIT_WAVES2 is a fence around a miscompile, not a tuning knob.  The knobs:
+// TCLB_STAGE_WAVES (build variants "sw2", "sw3"): floor of every full-grid stage kernel.
+// A kernel just past 256 VGPRs runs at 1 wave/SIMD; the cap trades that for spills (A/B
+// of the register-heavy collisions, e.g. the tePSM CHT collide).  0 = no cap (default).
 #ifndef TCLB_STAGE_WAVES
 #define TCLB_STAGE_WAVES 0
 #endif
-template <class Model, class R, class S, int STG, bool GLOB, int CLS = 0>
-#if TCLB_STAGE_WAVES > 0
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TCLB_STAGE_WAVES)))
-#else
-__global__ void __launch_bounds__(256)
-#endif
-k_stage(const Launch L) {
-  stage_body<Model, R, S, STG, GLOB, CLS>(L);
-}
-
-// Narrow-storage occupancy floor (build variant, -DTCLB_NARROW_WAVES=N): with fp32/fp16
+// TCLB_NARROW_WAVES (build variants "nw3", "nw4"): narrow-storage floor.  With fp32/fp16
 // storage each load moves half (a quarter) of the bytes, so a register-heavy kernel that
 // keeps HBM busy at 2 waves/SIMD in fp64 needs more waves in flight (Little's law);
-// amdgpu_waves_per_eu caps the VGPRs of the narrow-storage instantiations only.
-#ifdef TCLB_NARROW_WAVES
-template <class Model, class R, class S, int STG, bool GLOB>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TCLB_NARROW_WAVES)))
-k_stage_narrow(const Launch L) {
-  stage_body<Model, R, S, STG, GLOB>(L);
-}
+// the floor caps the VGPRs of the narrow-storage instantiations only.  0 = not requested.
+#ifndef TCLB_NARROW_WAVES
+#define TCLB_NARROW_WAVES 0
 #endif
-
-// Occupancy floor of the globals-integrating instantiations: the GLOB=true kernel keeps
-// the globals accumulators live through the whole node, which can push it past 256 VGPRs
-// into 1 wave/SIMD (pf_velocity mixed-shift: 266 VGPRs, 2.3x the plain step;
+// TCLB_GLOB_WAVES: floor of the globals-integrating instantiations.  The GLOB=true kernel
+// keeps the globals accumulators live through the whole node, which can push it past 256
+// VGPRs into 1 wave/SIMD (pf_velocity mixed-shift: 266 VGPRs, 2.3x the plain step;
 // profiles/README.md r03j/r03k).  amdgpu_waves_per_eu(W) caps it, W = the model's
 // GLOB_WAVES_ (DSL Model.glob_waves; 0 = no cap, for kernels far above 256 VGPRs where a
 // cap would spill heavily); -DTCLB_GLOB_WAVES=W overrides it for A/B builds.
@@ -255,24 +243,56 @@ k_stage_narrow(const Launch L) {
 #endif
 template <class Model>
 constexpr int glob_waves() { return TCLB_GLOB_WAVES >= 0 ? TCLB_GLOB_WAVES : Model::GLOB_WAVES_; }
-
-template <class Model, class R, class S, int STG, int W, int CLS = 0>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W))) k_stage_glob(const Launch L) {
-  stage_body<Model, R, S, STG, true, CLS>(L);
-}
-
-// Occupancy floor of the class-1 kernel of a split stage (A/B knob, build variant flag
-// -DTCLB_SPLIT_WAVES=n; 0 = none)
+// TCLB_SPLIT_WAVES (build variants "cw2".."cw4"): floor of the class-1 kernel of a split
+// stage (A/B knob; 0 = none)
 #ifndef TCLB_SPLIT_WAVES
 #define TCLB_SPLIT_WAVES 0
+#endif
+// TCLB_SPLIT_WAVES2: floor of the class-2 (boundary) kernels: 2 waves/SIMD, i.e. at most
+// 256 VGPRs and no AGPRs.  Without it the d3q27_tePSM_per_NEBB class-2 tile-list kernel of
+// the plain (globals-free) step (344 registers, 88 of them AGPRs) stores wrong h
+// populations on wall nodes on the MI355X, while the same node code is right as the
+// full-grid kernel, as the globals kernel, with this floor, and on the CPU under UBSan
+// (profiles/README.md r05m, r06s-u; build variant c2w0 reproduces it;
+// tests/test_kernel_budgets.py holds the fence).  The class-2 nodes are the few boundary
+// ones, so the spills of the floor cost nothing measurable.  The deferred-node kernel
+// (k_stage_deferred) runs the heavy path under the same floor (no AGPRs, the form
+// measured right; its spills cost little on the few nodes it runs).
+#ifndef TCLB_SPLIT_WAVES2
+#define TCLB_SPLIT_WAVES2 2
 #endif
 // A/B of the split itself (build variant nosplit): the stage as one kernel over all nodes
 #ifndef TCLB_NO_SPLIT
 #define TCLB_NO_SPLIT 0
 #endif
-template <class Model, class R, class S, int STG, bool GLOB, int W, int CLS>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W))) k_stage_w(const Launch L) {
+// CLS 0: the full-grid kernel (unsplit stages, and split ones under TCLB_NO_SPLIT); 1 / 2:
+// the class tile-list kernels; 3: the deferred-node kernel.  The two kernels of a
+// deferring stage raise a value of 0 to 1 in their declarators (k_stage_defer,
+// k_stage_deferred).
+template <class Model, class S, int STG, bool GLOB, int CLS>
+constexpr int stage_waves() {
+  if (CLS == 3) return TCLB_SPLIT_WAVES2;
+  if (GLOB && glob_waves<Model>() > 0) return glob_waves<Model>();
+  if (CLS == 2) return TCLB_SPLIT_WAVES2;
+  if (CLS == 1) return TCLB_SPLIT_WAVES;
+  return (TCLB_NARROW_WAVES > 0 && sizeof(S) < sizeof(double)) ? TCLB_NARROW_WAVES : TCLB_STAGE_WAVES;
+}
+
+// the full-grid kernels, one per source of the floor; launch_one checks at compile time
+// that the one it launches is declared with stage_waves<Model, S, STG, GLOB, 0>()
+template <class Model, class R, class S, int STG, bool GLOB, int CLS = 0>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TCLB_STAGE_WAVES)))
+k_stage(const Launch L) {
   stage_body<Model, R, S, STG, GLOB, CLS>(L);
+}
+template <class Model, class R, class S, int STG, bool GLOB>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TCLB_NARROW_WAVES)))
+k_stage_narrow(const Launch L) {
+  stage_body<Model, R, S, STG, GLOB>(L);
+}
+template <class Model, class R, class S, int STG, int W, int CLS = 0>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W))) k_stage_glob(const Launch L) {
+  stage_body<Model, R, S, STG, true, CLS>(L);
 }
 
 // ---------------------------------------------------------------- class tile lists
@@ -310,6 +330,11 @@ struct ClassTiles {
   unsigned* dq;     // deferring stages: [count][class-1 nodes handed to the CLS 3 kernel]
   unsigned n1, n2, total;
   unsigned long long used;
+  void release() {
+    hipFree(list);
+    hipFree(dq);
+    list = dq = nullptr;
+  }
 };
 
 // the tile lists of this launch's geometry, built on first use (one synchronising classify
@@ -332,12 +357,14 @@ inline bool class_tiles(const Launch& L, dim3 grid, dim3 block, hipStream_t s, C
       return true;
     }
   }
+  auto drop = [&](size_t i) {
+    cache[i].release();
+    cache.erase(cache.begin() + (long)i);
+  };
   // entries of an older identity of these node types are stale; keep at most 32 others
   for (size_t i = 0; i < cache.size();) {
     if (cache[i].flags == L.flags && cache[i].gen != L.flags_gen) {
-      hipFree(cache[i].list);
-      hipFree(cache[i].dq);
-      cache.erase(cache.begin() + (long)i);
+      drop(i);
     } else {
       i++;
     }
@@ -346,9 +373,7 @@ inline bool class_tiles(const Launch& L, dim3 grid, dim3 block, hipStream_t s, C
     size_t o = 0;
     for (size_t i = 1; i < cache.size(); i++)
       if (cache[i].used < cache[o].used) o = i;
-    hipFree(cache[o].list);
-    hipFree(cache[o].dq);
-    cache.erase(cache.begin() + (long)o);
+    drop(o);
   }
   const unsigned total = grid.x * grid.y * grid.z;
   unsigned char* d = nullptr;
@@ -378,20 +403,15 @@ inline bool class_tiles(const Launch& L, dim3 grid, dim3 block, hipStream_t s, C
   c.list = nullptr;
   c.dq = nullptr;
   // room for every node of the class-1 tiles (4 B per node)
-  if (Model::defer_stage(STG) &&
-      hipMalloc(&c.dq, ((size_t)l1.size() * block.x * block.y + 1) * sizeof(unsigned)) != hipSuccess)
-    return false;
+  ok = !Model::defer_stage(STG) ||
+       hipMalloc(&c.dq, ((size_t)l1.size() * block.x * block.y + 1) * sizeof(unsigned)) == hipSuccess;
   l1.insert(l1.end(), l2.begin(), l2.end());
-  if (!l1.empty()) {
-    if (hipMalloc(&c.list, l1.size() * sizeof(unsigned)) != hipSuccess) {
-      hipFree(c.dq);
-      return false;
-    }
-    if (hipMemcpy(c.list, l1.data(), l1.size() * sizeof(unsigned), hipMemcpyHostToDevice) != hipSuccess) {
-      hipFree(c.list);
-      hipFree(c.dq);
-      return false;
-    }
+  if (ok && !l1.empty())
+    ok = hipMalloc(&c.list, l1.size() * sizeof(unsigned)) == hipSuccess &&
+         hipMemcpy(c.list, l1.data(), l1.size() * sizeof(unsigned), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    c.release();
+    return false;
   }
   cache.push_back(c);
   out = c;
@@ -497,21 +517,10 @@ inline void launch_shape(const Launch& L, dim3& grid, dim3& block, int sbytes = 
   grid = dim3((w + bx - 1) / bx, (h + by - 1) / by, d);
 }
 
-// Occupancy floor of the class-2 (boundary) kernels: 2 waves/SIMD, i.e. at most 256
-// VGPRs and no AGPRs.  Without it the d3q27_tePSM_per_NEBB class-2 tile-list kernel of the
-// plain (globals-free) step (344 registers, 88 of them AGPRs) stores wrong h populations on
-// wall nodes on the MI355X, while the same node code is right as the full-grid kernel, as
-// the globals kernel, with this floor, and on the CPU under UBSan (profiles/README.md
-// r05m; build variant c2w0 reproduces it).  The class-2 nodes are the few boundary ones,
-// so the spills of the floor cost nothing measurable.
-#ifndef TCLB_SPLIT_WAVES2
-#define TCLB_SPLIT_WAVES2 2
-#endif
 // one class of a split stage: over the list of its tiles (no class tiles: every tile)
 template <class Model, class R, class S, int I, bool G, int CLS>
 inline void launch_class(const Launch& L, dim3 grid, dim3 block, hipStream_t s, const ClassTiles* ct) {
-  constexpr int W = (G && glob_waves<Model>() > 0) ? glob_waves<Model>()
-                                                   : (CLS == 1 ? TCLB_SPLIT_WAVES : TCLB_SPLIT_WAVES2);
+  constexpr int W = stage_waves<Model, S, I, G, CLS>();
   const unsigned n = !ct ? grid.x * grid.y * grid.z : (CLS == 1 ? ct->n1 : ct->n2);
   if (n == 0) return;
   // every tile: no list (the list entry is a dependent load at the start of each
@@ -540,15 +549,13 @@ inline bool launch_one(const Launch& L, dim3 grid, dim3 block, hipStream_t s) {
       // queue lives with the tile lists (no lists: nothing to run the stage with)
       if (!ct || !ct->dq) return false;
       if (ct->n1 > 0) {
-        constexpr int W = (G && glob_waves<Model>() > 0) ? glob_waves<Model>() : TCLB_SPLIT_WAVES;
+        constexpr int W = stage_waves<Model, S, I, G, 1>();
         const unsigned* list = ct->n1 == ct->total ? nullptr : ct->list;
         if (hipMemsetAsync(ct->dq, 0, sizeof(unsigned), s) != hipSuccess) return false;
         k_stage_defer<Model, R, S, I, G, W><<<dim3(ct->n1), block, 0, s>>>(L, list, ct->n1, grid.x, grid.y, ct->dq);
-        // the heavy path under the class-2 floor (no AGPRs, the form measured right; its
-        // spills cost little on the few nodes it runs)
         const unsigned long long cap = (unsigned long long)ct->n1 * block.x * block.y;
         const unsigned dg = (unsigned)((cap + 255) / 256 < DEFER_GRID ? (cap + 255) / 256 : DEFER_GRID);
-        k_stage_deferred<Model, R, S, I, TCLB_SPLIT_WAVES2><<<dim3(dg), dim3(256), 0, s>>>(L, ct->dq);
+        k_stage_deferred<Model, R, S, I, stage_waves<Model, S, I, false, 3>()><<<dim3(dg), dim3(256), 0, s>>>(L, ct->dq);
       }
       launch_class<Model, R, S, I, G, 2>(L, grid, block, s, ct);
     } else {
@@ -557,16 +564,22 @@ inline bool launch_one(const Launch& L, dim3 grid, dim3 block, hipStream_t s) {
     }
     return true;
   }
-  if constexpr (G && glob_waves<Model>() > 0) {
-    k_stage_glob<Model, R, S, I, glob_waves<Model>()><<<grid, block, 0, s>>>(L);
+  // the full-grid kernel declared with the floor W.  The code after a returning
+  // "if constexpr" is still instantiated, so each check holds for the launches it guards
+  // only (GLOBW, NARROW: an earlier branch has launched already).
+  constexpr int W = stage_waves<Model, S, I, G, 0>();
+  constexpr bool GLOBW = G && glob_waves<Model>() > 0;
+  constexpr bool NARROW = TCLB_NARROW_WAVES > 0 && sizeof(S) < sizeof(double);
+  if constexpr (GLOBW) {
+    k_stage_glob<Model, R, S, I, W><<<grid, block, 0, s>>>(L);
     return true;
   }
-#ifdef TCLB_NARROW_WAVES
-  if constexpr (sizeof(S) < sizeof(double)) {
+  if constexpr (NARROW) {
+    static_assert(GLOBW || W == TCLB_NARROW_WAVES, "k_stage_narrow does not carry the floor of stage_waves");
     k_stage_narrow<Model, R, S, I, G><<<grid, block, 0, s>>>(L);
     return true;
   }
-#endif
+  static_assert(GLOBW || NARROW || W == TCLB_STAGE_WAVES, "k_stage does not carry the floor of stage_waves");
   k_stage<Model, R, S, I, G><<<grid, block, 0, s>>>(L);
   return true;
 }
