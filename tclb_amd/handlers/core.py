@@ -401,13 +401,40 @@ class Log(Callback):
 
 @register("Failcheck")
 class Failcheck(Callback):
-    """reference cbFailcheck (src/Handlers/cbFailcheck.cpp:5-93): NaN scan, LOR, last words"""
+    """reference cbFailcheck (src/Handlers/cbFailcheck.cpp:5-93): NaN scan, LOR, last words.
+
+    ``dx dy dz nx ny nz`` restrict the scan to a region of the lattice, read like the
+    region of <VTK> (negative values count from the far side; the reference leaves absent
+    nx/ny/nz uninitialised, here they default to the rest of the lattice).  Each rank
+    tests the part of the region inside its own box; a rank with none of it reports clean.
+    A region scan skips adjoint quantities as the reference does; without region
+    attributes every selected quantity is scanned over the whole lattice, as before.  The
+    test is ``isfinite`` (the reference tests isnan only), so an overflow to infinity
+    stops the run as well."""
 
     def init(self):
         super().init()
         self.active = False
         self.what = _what(self.node)
+        self.reg = None
+        if any(self.node.get(a) is not None for a in ("dx", "dy", "dz", "nx", "ny", "nz")):
+            self.reg = _region_attrs(self, self.solver.total)
+            if self.reg[3] * self.reg[4] * self.reg[5] == 0:
+                raise HandlerError(f"{self.node.tag} region has size 0")
         return 0
+
+    def _local(self, a):
+        """the part of the (ncomp, nz, ny, nx) tensor inside the region, None if empty"""
+        if self.reg is None:
+            return a
+        lat = self.solver.lattice
+        sl = []
+        for off, n, r0, rn in zip(lat.slab.offset, lat.shape, self.reg[:3], self.reg[3:]):
+            lo, hi = max(r0 - off, 0), min(r0 + rn - off, n)
+            if hi <= lo:
+                return None
+            sl.append(slice(lo, hi))
+        return a[:, sl[2], sl[1], sl[0]]
 
     def do_it(self):
         if self.active:
@@ -417,9 +444,11 @@ class Failcheck(Callback):
         fin = False
         import torch
         for q in s.model.quantities:
+            if q.adjoint and self.reg is not None:
+                continue
             if "all" in self.what or q.name in self.what:
-                a = s.lattice.quantity(q.name)
-                bad = 0.0 if bool(torch.isfinite(a).all().item()) else 1.0
+                a = self._local(s.lattice.quantity(q.name))
+                bad = 0.0 if a is None or bool(torch.isfinite(a).all().item()) else 1.0
                 if s.comm.allreduce_scalar(bad, "max") > 0:
                     log.notice(f"Checking {q.name} discovered NaN")
                     fin = True
@@ -641,13 +670,37 @@ class Sample(Callback):
 
 @register("PID")
 class PID(Callback):
-    """reference cbPID (src/Handlers/cbPID.cpp:94-122): drive a (zonal) setting so that a
-    global reaches a target."""
+    """reference cbPID (src/Handlers/cbPID.cpp:5-131): drive a (zonal) setting so that a
+    global reaches a target.
+
+    Reference grammar (selected by ``integral=``): ``<PID integral="Global" target=
+    control="ZonalSetting" [zone=] [IntegrationTime=] [DerivativeTime=] [scale=]
+    Iterations=>``.  With DT the callback interval and sval the control's value at init
+    (zone ``zone``, or zone 0), every firing does
+
+        err = target - G;  integral += (old_err + err) DT/2;  derivative = (err - old_err)/DT
+        control = err + integral/IntegrationTime + derivative DerivativeTime
+        setting = sval + control scale        (in ``zone``, or in every zone)
+
+    sval is read once, as in the reference (its per-firing re-read is commented out).  The
+    globals are all-reduced on every rank, so the reference's broadcast of ``control`` from
+    rank 0 is not needed.
+
+    The older spelling ``<PID <Global>="target" control= P= I= D=>`` keeps its own law.
+    Both force the globals on the last step of each segment (ITER_LASTGLOB) and restore
+    the iteration type when they are unstacked."""
 
     def init(self):
         super().init()
+        from ..solver import ITER_LASTGLOB
         n = self.node
         s = self.solver
+        self.old_iter_type = s.iter_type
+        self.reference_form = n.get("integral") is not None
+        if self.reference_form:
+            self._init_reference()
+            s.iter_type |= ITER_LASTGLOB
+            return 0
         self.control = n.get("control")
         self.zone = n.get("zone")
         self.what = None
@@ -664,11 +717,61 @@ class PID(Callback):
         self.DT = float(n.get("DerivativeTime", n.get("DT", "0")))
         self.integral = 0.0
         self.prev = None
-        from ..solver import ITER_LASTGLOB
         s.iter_type |= ITER_LASTGLOB
         return 0
 
+    def _init_reference(self):
+        n = self.node
+        s = self.solver
+        lat = s.lattice
+        self.what = n.get("integral")
+        if n.get("target") is None:
+            raise HandlerError("No target value provided in the PID element")
+        self.target = s.units.alt(n.get("target"))
+        if self.what == "":
+            raise HandlerError("Name of the global not provided in the PID element")
+        if all(g.name != self.what for g in s.model.globals_):
+            raise HandlerError(f"Unknown global name {self.what} in the PID element")
+        self.control = n.get("control", "")
+        self.zone = n.get("zone") or None
+        if self.zone is not None and self.zone not in lat.zone_names:
+            raise HandlerError(f"Unknown zone {self.zone} (found while setting parameter {self.control})")
+        if self.control == "":
+            raise HandlerError(f"No zonal setting supplied for control in {n.tag}")
+        st = s.model.setting(self.control)
+        if st is None or not st.zonal:
+            raise HandlerError(f"{self.control} is not a valid zonal setting supplied for control in {n.tag}")
+        self.itime = s.units.alt(n.get("IntegrationTime", "1s"))
+        self.dtime = s.units.alt(n.get("DerivativeTime", "1s"))
+        self.scale = s.units.alt(n.get("scale", "1s"))
+        self.integral = 0.0
+        self.old_err = 0.0
+        self.DT = self.every_iter
+        if not self.DT:
+            raise HandlerError(f"{n.tag} needs Iterations (the interval is the integration step)")
+        self.sval = lat.get_setting(self.control, zone=self.zone)
+
+    def _do_reference(self):
+        s = self.solver
+        val = s.lattice.globals.get(self.what, 0.0)
+        err = self.target - val
+        log.output(f"PID criterium : {val:g} --> {self.target:g} (error: {err:g})")
+        self.integral = self.integral + (self.old_err + err) * self.DT / 2.0
+        derivative = (err - self.old_err) / self.DT
+        control = err + self.integral / self.itime + derivative * self.dtime
+        self.old_err = err
+        nval = self.sval + control * self.scale
+        log.output(f"PID setting   : {self.sval:g} --> {nval:g} (control: {control:g})")
+        s.lattice.set_setting(self.control, nval, zone=self.zone)
+        return 0
+
+    def finish(self):
+        self.solver.iter_type = self.old_iter_type
+        return super().finish()
+
     def do_it(self):
+        if self.reference_form:
+            return self._do_reference()
         s = self.solver
         v = s.lattice.globals.get(self.what, 0.0)
         err = self.target - v
@@ -682,23 +785,68 @@ class PID(Callback):
 
 @register("Keep")
 class Keep(Callback):
-    """reference cbKeep (src/Handlers/cbKeep.cpp:45-66): objective constraint weight"""
+    """reference cbKeep (src/Handlers/cbKeep.cpp:5-73): objective constraint weight.
+
+    Reference grammar (selected by ``What=``): ``<Keep What="Global" Above=|Below=|Equal=
+    [Force=] Iterations=>``; thresholds are plain numbers.  With v = (thr - G) Force the
+    global's ``<What>InObj`` weight is set in every zone to v if v > 0 else 0 (Above),
+    v if v < 0 else 0 (Below) or v (Equal).  The reference broadcasts that double as
+    MPI_INT from rank 0; here every rank has the all-reduced global and computes the
+    double itself.
+
+    The older spelling ``<Keep <Global>Above=|Below=|Equal= Force=>`` keeps its arithmetic.
+    Both force the globals on the last step of each segment (ITER_LASTGLOB) and restore
+    the iteration type when they are unstacked."""
 
     def init(self):
         super().init()
+        from ..solver import ITER_LASTGLOB
         n = self.node
         s = self.solver
+        self.old_iter_type = s.iter_type
+        self.what = n.get("What")
         self.items = []
-        for g in s.model.globals_:
-            for kind in ("Above", "Below", "Equal"):
-                v = n.get(g.name + kind)
-                if v is not None:
-                    self.items.append((g.name, kind, s.units.alt(v)))
+        if self.what is not None:
+            if all(g.name != self.what for g in s.model.globals_):
+                raise HandlerError(f"Unknown Global {self.what} in {n.tag}")
+            st = s.model.setting(self.what + "InObj")
+            if st is None or not st.zonal:
+                raise HandlerError(f"Global {self.what} has no {self.what}InObj setting (in {n.tag})")
+            if n.get("Above") is not None:
+                self.thr, self.my_type = float(n.get("Above")), 1
+            elif n.get("Below") is not None:
+                self.thr, self.my_type = float(n.get("Below")), -1
+            elif n.get("Equal") is not None:
+                self.thr, self.my_type = float(n.get("Equal")), 0
+            else:
+                raise HandlerError(f"{n.tag} should have Above, Below or Equal attribute")
+        else:
+            for g in s.model.globals_:
+                for kind in ("Above", "Below", "Equal"):
+                    v = n.get(g.name + kind)
+                    if v is not None:
+                        self.items.append((g.name, kind, s.units.alt(v)))
+            if not self.items:
+                raise HandlerError(f"No What attribute in {n.tag}")
         self.force = float(n.get("Force", "1"))
+        s.iter_type |= ITER_LASTGLOB
         return 0
+
+    def finish(self):
+        self.solver.iter_type = self.old_iter_type
+        return super().finish()
 
     def do_it(self):
         s = self.solver
+        if self.what is not None:
+            v = s.lattice.globals.get(self.what, 0.0)
+            log.output(f"Keep: {v:e} compared to {self.thr:e}")
+            v = (self.thr - v) * self.force
+            w = 0.0
+            if self.my_type == 0 or (self.my_type > 0 and v > 0) or (self.my_type < 0 and v < 0):
+                w = v
+            s.lattice.set_setting(self.what + "InObj", w)
+            return 0
         for name, kind, thr in self.items:
             v = s.lattice.globals.get(name, 0.0)
             w = self.force * (thr - v)

@@ -11,6 +11,7 @@ place of NLopt, maximising the Objective like the reference's nlopt_set_max_obje
 from __future__ import annotations
 
 import math
+import os
 from typing import List
 
 import numpy as np
@@ -633,32 +634,130 @@ class Optimize(_Optimizer):
 
 @register("FDTest")
 class FDTest(_Optimizer):
-    """finite-difference check of the adjoint gradient (reference acFDTest): prints and
-    stores (parameter, adjoint, finite difference) rows; order 2/4/6 central differences"""
+    """finite-difference check of the adjoint gradient (reference acFDTest,
+    src/Handlers/acFDTest.cpp:5-146): prints and stores (parameter, adjoint, finite
+    difference) rows in ``solver.fdtest``; order 2/4/6 central differences.
+
+    Sweep mode, selected by any of ``hmin``, ``hmax``, ``levels`` (absent ones default to
+    1e-11, 1, 24 as in the reference): parameter k is stepped by
+    h = dx[k] exp(ln hmin + (ln hmax - ln hmin) ih/(levels - 1)), dx[k] = (upper - lower)/2,
+    for ih = 0..levels-1, one ``fdtest`` row per parameter and level (the finite difference
+    being the highest-order one).  Without those attributes the step is the single
+    absolute ``h`` (default 1e-6), not scaled by dx: a deliberate deviation from the
+    reference's 24-level default, so that existing cases keep their cost and results.
+
+    ``parameters``: ``a:b``, ``a:``, ``:b`` (inclusive) or a single index ``a`` (the
+    reference leaves the count at "all" for a bare ``a``, which puts every a > 0 out of
+    bounds; here it selects that one parameter).
+
+    Both modes write ``<outpath>_FD_test.csv`` on rank 0 in the reference's layout: one row
+    per parameter and step with the parameter's value, its adjoint gradient, h, the
+    objective at start + m h for m = -o..o (o = order/2; the reference labels the m < 0
+    columns "RightObj") and the central differences of order 2o down to 2 over h.  Numbers
+    are written with 16 significant digits like the reference's, except the objective
+    columns, which carry 17: the differences cancel most of their digits, and with 17 the
+    file holds exactly the doubles that were differenced."""
+
+    def _selection(self, npar):
+        sel = self.node.get("parameters")
+        start, num = 0, npar
+        if sel:
+            a, colon, b = sel.partition(":")
+            if not colon:
+                start, num = int(a), 1
+            else:
+                start = int(a) if a else 0
+                num = (int(b) + 1 if b else npar) - start
+        if num < 1 or start < 0:
+            raise HandlerError("You need at least one parameter in FDTest")
+        if start >= npar or start + num > npar:
+            raise HandlerError("Parameter out of bounds in FDTest")
+        return list(range(start, start + num))
+
+    @staticmethod
+    def _central(val, o):
+        """central differences (not yet divided by h) of the values val[m + o], m = -o..o,
+        highest order first (reference acFDTest.cpp:129-139, a switch falling through)"""
+        v = lambda m: val[o + m]   # noqa: E731
+        out = []
+        if o >= 3:
+            out.append((v(3) + 9 * (-v(2) + 5 * (v(1) - v(-1)) + v(-2)) - v(-3)) / 60)
+        if o >= 2:
+            out.append((-v(2) + 8 * (v(1) - v(-1)) + v(-2)) / 12)
+        out.append((v(1) - v(-1)) / 2)
+        return out
+
+    def _write_csv(self, o, lines):
+        s = self.solver
+        if s.rank != 0:
+            return
+        fn = f"{s.outpath}_FD_test.csv"
+        os.makedirs(os.path.dirname(fn) or ".", exist_ok=True)
+        head = "Parameter, Value, Gradient, H"
+        head += "".join(f", RightObj{k}" for k in range(o, 0, -1)) + ", Objective"
+        head += "".join(f", LeftObj{k}" for k in range(1, o + 1))
+        head += "".join(f", CentralDiff{k}" for k in range(o, 0, -1))
+        with open(fn, "w") as f:
+            f.write(head + "\n")
+            for k, x, g, h, val in lines:
+                row = "%d, %.16g, %.16g, %.16g" % (k, x, g, h)
+                row += "".join(", %.17g" % v for v in val)
+                row += "".join(", %.16g" % (d / h) for d in self._central(val, o))
+                f.write(row + "\n")
 
     def init(self):
         super().init()
-        x0, _, _ = self._prepare()
-        order = max(2, min(6, int(self.node.get("order", "2"))))
+        n = self.node
+        x0, lo, hi = self._prepare()
+        order = max(2, min(6, int(n.get("order", "2"))))
         order += order % 2
-        h = float(self.node.get("h", "1e-6"))
-        sel = self.node.get("parameters")
-        idx = list(range(x0.size))
-        if sel:
-            a, _, b = sel.partition(":")
-            idx = list(range(int(a or 0), int(b) + 1 if b else x0.size)) if ":" in sel else [int(sel)]
+        o = order // 2
+        idx = self._selection(x0.size)
+        sweep = any(n.get(a) is not None for a in ("hmin", "hmax", "levels"))
+        if sweep:
+            hmin, hmax = float(n.get("hmin", "1e-11")), float(n.get("hmax", "1"))
+            levels = int(n.get("levels", "24"))
+            if hmin <= 0 or hmax <= 0:
+                raise HandlerError("You need to provide a H > 0 in FDTest")
+            if levels < 2:
+                raise HandlerError("You need to provide a levels >= 2 in FDTest")
+            lmin, lmax = math.log(hmin), math.log(hmax)
+            dx = (hi - lo) / 2.0
+        else:
+            h = float(n.get("h", "1e-6"))
         J0, g0 = self._evaluate(x0)
-        coef = {2: [(1, 0.5)], 4: [(1, 2 / 3), (2, -1 / 12)], 6: [(1, 0.75), (2, -0.15), (3, 1 / 60)]}[order]
-        rows = []
-        for i in idx:
-            d = 0.0
-            for k, c in coef:
-                xp, xm = x0.copy(), x0.copy()
-                xp[i] += k * h
-                xm[i] -= k * h
-                d += c * (self._evaluate(xp)[0] - self._evaluate(xm)[0]) / h
-            rows.append((i, float(g0[i]), d))
-            log.notice(f"FDTest parameter {i}: adjoint {g0[i]:.10g}  finite difference {d:.10g}")
+        rows, lines = [], []
+        if sweep:
+            for k in idx:
+                for ih in range(levels):
+                    hk = float(dx[k]) * math.exp(lmin + ((lmax - lmin) * ih) / (levels - 1))
+                    val = []
+                    for m in range(-o, o + 1):
+                        if m == 0:
+                            val.append(J0)
+                            continue
+                        x = x0.copy()
+                        x[k] = x0[k] + m * hk
+                        val.append(self._evaluate(x)[0])
+                    d = self._central(val, o)[0] / hk
+                    rows.append((k, float(g0[k]), d))
+                    lines.append((k, float(x0[k]), float(g0[k]), hk, val))
+                    log.notice(f"FDTest parameter {k} h {hk:g}: adjoint {g0[k]:.10g}  finite difference {d:.10g}")
+        else:
+            coef = {2: [(1, 0.5)], 4: [(1, 2 / 3), (2, -1 / 12)], 6: [(1, 0.75), (2, -0.15), (3, 1 / 60)]}[order]
+            for i in idx:
+                d = 0.0
+                val = {0: J0}
+                for k, c in coef:
+                    xp, xm = x0.copy(), x0.copy()
+                    xp[i] += k * h
+                    xm[i] -= k * h
+                    val[k], val[-k] = self._evaluate(xp)[0], self._evaluate(xm)[0]
+                    d += c * (val[k] - val[-k]) / h
+                rows.append((i, float(g0[i]), d))
+                lines.append((i, float(x0[i]), float(g0[i]), h, [val[m] for m in range(-o, o + 1)]))
+                log.notice(f"FDTest parameter {i}: adjoint {g0[i]:.10g}  finite difference {d:.10g}")
+        self._write_csv(o, lines)
         self.solver.fdtest = rows
         self._evaluate(x0)
         return 0
@@ -691,20 +790,72 @@ class OptSolve(GenericAction):
         return 0
 
 
-@register("Threshold", "ThresholdNow")
-class Threshold(Action):
-    """topology thresholding of the design parameters: p <- (p > level), level from the
-    ``Level`` attribute or the Threshold setting (reference acThreshold/acThresholdNow)"""
+def _threshold_start(h):
+    """the design parameters to threshold (reference acThreshold.cpp:21-42)"""
+    s = h.solver
+    if s.model.setting("Threshold") is None:
+        raise HandlerError("'Threshold' is not a setting")
+    start = _get_all(s, PAR_GET)
+    if start.size == 0:
+        raise HandlerError(f"{h.node.tag}: No parameters defined!")
+    return start
+
+
+@register("Threshold")
+class Threshold(GenericAction):
+    """topology thresholding of the design parameters.
+
+    ``<Threshold Levels="N"> children </Threshold>`` (reference acThreshold,
+    src/Handlers/acThreshold.cpp:5-52) sweeps N >= 2 levels th = i/(N-1): the Threshold
+    setting is set to th, the parameters to 1.0 where their value at entry exceeds th
+    and 0.0 elsewhere, and the children run once per level.
+
+    Without ``Levels`` the reference would sweep 5 levels.  Here, deliberately, a bare
+    ``<Threshold [Level=]/>`` thresholds once, p <- (p > level) to the upper / lower
+    bounds, with the level from ``Level`` or the Threshold setting and no children run,
+    so that existing cases do not change."""
 
     def init(self):
         super().init()
         s = self.solver
+        if self.node.get("Levels") is not None:
+            levels = int(self.node.get("Levels"))
+            if levels < 2:
+                raise HandlerError(f"{self.node.tag} needs Levels >= 2")
+            start = _threshold_start(self)
+            for i in range(levels):
+                th = (1.0 * i) / (levels - 1)
+                s.lattice.set_setting("Threshold", th)
+                _set_all(s, np.where(start > th, 1.0, 0.0))
+                log.notice(f"Threshold level {th:g}: {int((start > th).sum())} of {start.size} parameters set to 1")
+                if self.execute_internal():
+                    raise HandlerError(f"Something wrong in {self.node.tag} at level {th:g}")
+                self.unstack()
+            return 0
         lvl = self.node.get("Level")
         level = float(lvl) if lvl is not None else s.lattice.get_setting("Threshold")
         x = _get_all(s, PAR_GET)
         lo, hi = _get_all(s, PAR_LOWER), _get_all(s, PAR_UPPER)
         _set_all(s, np.where(x > level, hi, lo))
         log.notice(f"Threshold at {level}: {int((x > level).sum())} of {x.size} parameters set to upper bound")
+        return 0
+
+
+@register("ThresholdNow")
+class ThresholdNow(Action):
+    """``<ThresholdNow [Level="0.5"]/>`` (reference acThresholdNow,
+    src/Handlers/acThresholdNow.cpp:5-44): set the Threshold setting to Level and the
+    design parameters to 1.0 where they exceed it, 0.0 elsewhere.  Level is a float (the
+    reference parses it as an integer, which only allows 0 and 1)."""
+
+    def init(self):
+        super().init()
+        s = self.solver
+        level = float(self.node.get("Level", "0.5"))
+        start = _threshold_start(self)
+        s.lattice.set_setting("Threshold", level)
+        _set_all(s, np.where(start > level, 1.0, 0.0))
+        log.notice(f"ThresholdNow at {level:g}: {int((start > level).sum())} of {start.size} parameters set to 1")
         return 0
 
 

@@ -51,9 +51,12 @@ def handler_elements() -> Dict[str, List[str]]:
         for k in inspect.getmro(cls):
             if k.__module__.startswith("tclb_amd"):
                 try:
-                    attrs.update(_ATTR_RE.findall(inspect.getsource(k)))
+                    src = inspect.getsource(k)
                 except (OSError, TypeError):
-                    pass
+                    continue
+                attrs.update(_ATTR_RE.findall(src))
+                if "_region_attrs(" in src:     # handlers/core.py _region_attrs reads the region
+                    attrs.update(("dx", "dy", "dz", "nx", "ny", "nz"))
         out[name] = sorted(attrs)
     return out
 
