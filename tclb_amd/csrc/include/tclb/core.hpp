@@ -419,6 +419,53 @@ TCLB_FN void sample_node(NodeT& n, const SamplePlan& P, double* o) {
   }
 }
 
+// Box plan of the output gather (Lattice.gather): every node of the window
+// Launch.xlo..zhi evaluates the nq quantities after one pop() and writes entry i to
+// out[i][c * cs + ix * sx + iy * sy + iz * sz] (element strides, window-relative
+// indices), scaled and converted to the entry's element type.  The strides carry the
+// layout: interleaved vectors (nz,ny,nx,nc) are cs = 1, sx = nc; planar ones
+// (nc,nz,ny,nx) are cs = nx*ny*nz, sx = 1.  The box counterpart of SamplePlan; passed to
+// the GPU kernel by value next to the Launch (kernel arguments are limited to 4 KiB).
+constexpr int GATHER_F64 = 0, GATHER_F32 = 1;
+struct GatherPlan {
+  int nq, reserved;
+  int q[SAMPLE_MAXQ], ncomp[SAMPLE_MAXQ], otype[SAMPLE_MAXQ];
+  double scale[SAMPLE_MAXQ];
+  void* out[SAMPLE_MAXQ];
+  long long cs[SAMPLE_MAXQ], sx[SAMPLE_MAXQ], sy[SAMPLE_MAXQ], sz[SAMPLE_MAXQ];
+};
+static_assert(sizeof(Launch) + sizeof(GatherPlan) <= 4096, "k_gather's arguments exceed the kernarg segment");
+
+// every quantity of the plan at node n, window-relative (ix, iy, iz) (shared by both
+// executors): one pop(), the populations stay in registers for all entries.  The product is the one of k_quantity, taken in the compute type; the
+// output is written once and read back by a copy only: streaming stores.
+template <class NodeT>
+TCLB_FN void gather_node(NodeT& n, const GatherPlan& P, int ix, int iy, int iz) {
+  typedef typename NodeT::real_t R;
+  n.pop();
+  for (int i = 0; i < P.nq; i++) {
+    R v[3] = {R(0), R(0), R(0)};
+    // on a copy of the popped node: a model's getter may update the node it is called on
+    // (the cm_cht getU() shifts the populations it reads), and every entry has to see the
+    // state k_quantity sees after its own pop()
+    NodeT m(n);
+    m.get_quantity(P.q[i], v);
+    const long long idx = ix * P.sx[i] + iy * P.sy[i] + iz * P.sz[i];
+    const long long cs = P.cs[i];
+    const int nc = P.ncomp[i];
+    const R s = R(P.scale[i]);
+    if (P.otype[i] == GATHER_F32) {
+      float* o = (float*)P.out[i] + idx;
+      TCLB_UNROLL for (int c = 0; c < 3; c++)
+        if (c < nc) store_stream(o + c * cs, (float)(v[c] * s));
+    } else {
+      double* o = (double*)P.out[i] + idx;
+      TCLB_UNROLL for (int c = 0; c < 3; c++)
+        if (c < nc) store_stream(o + c * cs, (double)(v[c] * s));
+    }
+  }
+}
+
 // Multi-step driver: nsteps of one action (stage list) with A/B snapshot swapping and no
 // host round trip per step (reference Lattice::Iterate, src/Lattice.cu.Rt:900-989).  Used
 // when no halo exchange is needed between stages (one rank, periodic wrap in-kernel);
@@ -482,8 +529,8 @@ inline int prec_dispatch(int prec, F&& f) {
   }
 }
 
-// C exports common to both executors (each defines tclb::exec::run_stage, run_quantity
-// and run_sample for its device).
+// C exports common to both executors (each defines tclb::exec::run_stage, run_quantity,
+// run_sample and run_gather for its device).
 #define TCLB_EXPORT_COMMON(NAME, MODEL)                                                       \
   extern "C" int tclb_##NAME##_run(const tclb::Launch* L, int prec) {                         \
     return tclb::prec_dispatch(prec, [&](auto t) {                                            \
@@ -516,6 +563,13 @@ inline int prec_dispatch(int prec, F&& f) {
     });                                                                                       \
   }                                                                                           \
   extern "C" int tclb_##NAME##_sizeof_sample_plan() { return (int)sizeof(tclb::SamplePlan); } \
+  extern "C" int tclb_##NAME##_gather(const tclb::Launch* L, int prec, const tclb::GatherPlan* P) { \
+    return tclb::prec_dispatch(prec, [&](auto t) {                                            \
+      using T = decltype(t);                                                                  \
+      return tclb::exec::run_gather<MODEL, typename T::R, typename T::S>(*L, *P);             \
+    });                                                                                       \
+  }                                                                                           \
+  extern "C" int tclb_##NAME##_sizeof_gather_plan() { return (int)sizeof(tclb::GatherPlan); } \
   extern "C" int tclb_##NAME##_sizeof_launch() { return (int)sizeof(tclb::Launch); }
 
 // Globals accumulation of one node (the emitted AddTo<global>).  `g` is the executor's

@@ -89,6 +89,21 @@ inline int run_sample(const Launch& L, const SamplePlan& P) {
   return 0;
 }
 
+template <class Model, class R, class S>
+inline int run_gather(const Launch& L, const GatherPlan& P) {
+  if (P.nq < 0 || P.nq > SAMPLE_MAXQ) return -3;
+  if (P.nq == 0) return 0;
+#pragma omp parallel for collapse(2) schedule(static)
+  for (int z = L.zlo; z < L.zhi; z++)
+    for (int y = L.ylo; y < L.yhi; y++)
+      for (int x = L.xlo; x < L.xhi; x++) {
+        typename Model::template NodeT<R, S, false>::G_ g[1];
+        typename Model::template NodeT<R, S, false> n(L, x, y, z, g);
+        gather_node(n, P, x - L.xlo, y - L.ylo, z - L.zlo);
+      }
+  return 0;
+}
+
 }  // namespace exec
 }  // namespace tclb
 

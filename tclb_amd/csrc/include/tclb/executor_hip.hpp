@@ -492,6 +492,20 @@ __global__ void __launch_bounds__(64) k_sample(const Launch L, const SamplePlan 
   sample_node(n, P, P.out + ((long long)P.row * P.np + p) * P.width);
 }
 
+// Output gather: one thread per node of the window, every quantity of the plan after one
+// pop() (core.hpp GatherPlan, gather_node).  As in k_quantity a wave is one 64-node row
+// segment (block x is a multiple of 64, launch_shape) and y is wave-uniform.
+template <class Model, class R, class S>
+__global__ void __launch_bounds__(256) k_gather(const Launch L, const GatherPlan P) {
+  const int x = L.xlo + (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  const int y = __builtin_amdgcn_readfirstlane(L.ylo + (int)(blockIdx.y * blockDim.y + threadIdx.y));
+  const int z = L.zlo + (int)blockIdx.z;
+  if (x >= L.xhi || y >= L.yhi) return;
+  typename Model::template NodeT<R, S, false>::G_ g[1];
+  typename Model::template NodeT<R, S, false> n(L, x, y, z, g);
+  gather_node(n, P, x - L.xlo, y - L.ylo, z - L.zlo);
+}
+
 // Default shapes from on-device A/B (profiles/r01_tune_*): fp64 storage 128x2, fp32 256x1.
 inline void launch_shape(const Launch& L, dim3& grid, dim3& block, int sbytes = 8) {
   const int w = L.xhi - L.xlo, h = L.yhi - L.ylo, d = L.zhi - L.zlo;
@@ -616,6 +630,16 @@ template <class Model, class R, class S>
 inline int run_sample(const Launch& L, const SamplePlan& P) {
   if (P.np <= 0 || P.row < 0 || P.row >= P.rows) return 0;
   k_sample<Model, R, S><<<dim3((P.np + 63) / 64), dim3(64), 0, (hipStream_t)L.stream>>>(L, P);
+  return (int)hipGetLastError();
+}
+
+template <class Model, class R, class S>
+inline int run_gather(const Launch& L, const GatherPlan& P) {
+  if (P.nq < 0 || P.nq > SAMPLE_MAXQ) return -3;
+  if (P.nq == 0 || L.xhi <= L.xlo || L.yhi <= L.ylo || L.zhi <= L.zlo) return 0;
+  dim3 grid, block;
+  launch_shape(L, grid, block, (int)sizeof(S));
+  k_gather<Model, R, S><<<grid, block, 0, (hipStream_t)L.stream>>>(L, P);
   return (int)hipGetLastError();
 }
 

@@ -423,18 +423,18 @@ class Failcheck(Callback):
                 raise HandlerError(f"{self.node.tag} region has size 0")
         return 0
 
-    def _local(self, a):
-        """the part of the (ncomp, nz, ny, nx) tensor inside the region, None if empty"""
-        if self.reg is None:
-            return a
+    def _local_region(self):
+        """the part of the region inside this rank's box, in local interior coordinates
+        (x0, y0, z0, nx, ny, nz); None if the rank holds none of it"""
         lat = self.solver.lattice
-        sl = []
-        for off, n, r0, rn in zip(lat.slab.offset, lat.shape, self.reg[:3], self.reg[3:]):
-            lo, hi = max(r0 - off, 0), min(r0 + rn - off, n)
-            if hi <= lo:
+        lo, n = [], []
+        for off, m, r0, rn in zip(lat.slab.offset, lat.shape, self.reg[:3], self.reg[3:]):
+            a, b = max(r0 - off, 0), min(r0 + rn - off, m)
+            if b <= a:
                 return None
-            sl.append(slice(lo, hi))
-        return a[:, sl[2], sl[1], sl[0]]
+            lo.append(a)
+            n.append(b - a)
+        return tuple(lo + n)
 
     def do_it(self):
         if self.active:
@@ -443,16 +443,21 @@ class Failcheck(Callback):
         s = self.solver
         fin = False
         import torch
-        for q in s.model.quantities:
-            if q.adjoint and self.reg is not None:
-                continue
-            if "all" in self.what or q.name in self.what:
-                a = self._local(s.lattice.quantity(q.name))
-                bad = 0.0 if a is None or bool(torch.isfinite(a).all().item()) else 1.0
-                if s.comm.allreduce_scalar(bad, "max") > 0:
-                    log.notice(f"Checking {q.name} discovered NaN")
-                    fin = True
-                    break
+        sel = [q for q in s.model.quantities if not (q.adjoint and self.reg is not None)
+               and ("all" in self.what or q.name in self.what)]
+        part = None
+        if self.reg is not None:
+            # a region scan evaluates only the nodes of its local part, every selected
+            # quantity in one pass (Lattice.gather)
+            loc = self._local_region()
+            part = s.lattice.gather([q.name for q in sel], loc) if loc is not None else {}
+        for q in sel:
+            a = s.lattice.quantity(q.name) if part is None else part.get(q.name)
+            bad = 0.0 if a is None or bool(torch.isfinite(a).all().item()) else 1.0
+            if s.comm.allreduce_scalar(bad, "max") > 0:
+                log.notice(f"Checking {q.name} discovered NaN")
+                fin = True
+                break
         self.active = False
         if fin:
             log.notice("NaN value discovered. Executing final actions from the Failcheck element before full stop...")

@@ -27,8 +27,10 @@ def extent(reg) -> str:
 
 
 def write_vti(path: str, total_reg, reg, fields: List[Tuple[str, np.ndarray, int]], spacing: float = 1.0,
-              origin=(0.0, 0.0, 0.0)):
-    """fields: (name, array (nz,ny,nx) or (ncomp,nz,ny,nx), ncomp)"""
+              origin=(0.0, 0.0, 0.0), interleaved: bool = False):
+    """fields: (name, array (nz,ny,nx) or (ncomp,nz,ny,nx), ncomp); interleaved: vectors
+    come as (nz,ny,nx,ncomp), the layout of the file (Solver.output_fields), and are
+    encoded without a copy"""
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     with open(path, "w") as f:
         f.write('<?xml version="1.0"?>\n<VTKFile type="ImageData" version="0.1" byte_order="LittleEndian">\n')
@@ -37,7 +39,7 @@ def write_vti(path: str, total_reg, reg, fields: List[Tuple[str, np.ndarray, int
         f.write(f'<Piece Extent="{extent(reg)}">\n<CellData Scalars="rho" Vectors="velocity">\n')
         for name, arr, nc in fields:
             a = np.asarray(arr)
-            if nc > 1:
+            if nc > 1 and not interleaved:
                 a = np.moveaxis(a, 0, -1)  # (nz,ny,nx,nc) interleaved components
             t = _VTK_T[a.dtype]
             f.write(f'<DataArray type="{t}" Name="{name}" format="binary" encoding="base64" '

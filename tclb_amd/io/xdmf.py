@@ -35,15 +35,16 @@ def create(path: str, lay):
         pass
 
 
-def write_piece(path: str, region, lreg, fields, lay):
-    """pwrite this rank's sub-box `lreg` of every field into the shared file"""
+def write_piece(path: str, region, lreg, fields, lay, interleaved: bool = False):
+    """pwrite this rank's sub-box `lreg` of every field into the shared file; vectors come
+    as (nc, nz, ny, nx), or with interleaved=True as (nz, ny, nx, nc), the file's layout"""
     X0, Y0, Z0, NX, NY, NZ = region
     x0, y0, z0, nx, ny, nz = lreg
     fd = os.open(path, os.O_WRONLY)
     try:
         for (name, a, nc), (_, dt, _, off) in zip(fields, lay):
             a = np.asarray(a)
-            if nc > 1:
+            if nc > 1 and not interleaved:
                 a = np.moveaxis(a, 0, -1)            # (nz, ny, nx, nc)
             a = np.ascontiguousarray(a.astype(dt.newbyteorder("<"), copy=False))
             for k in range(nz):

@@ -17,6 +17,7 @@ src/Lattice.cu.Rt).  Differences by design:
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 import os
@@ -940,11 +941,15 @@ class Lattice:
         """to be called after any write into self.flags"""
         self.flags_version = next(_FLAGS_GEN)
 
-    def get_flags(self) -> np.ndarray:
-        """interior flags (nz, ny, nx) as unsigned"""
-        f = self.flags.cpu().numpy()
-        f = f.view(np.uint16 if self.model.flag_bits == 16 else np.uint32)
-        return self._interior(f)
+    def get_flags(self, region=None) -> np.ndarray:
+        """interior flags (nz, ny, nx) as unsigned; region (x0, y0, z0, nx, ny, nz) in local
+        interior coordinates: that window only, sliced on the device before the copy"""
+        ut = np.uint16 if self.model.flag_bits == 16 else np.uint32
+        if region is None:
+            return self._interior(self.flags.cpu().numpy().view(ut))
+        x0, y0, z0, wx, wy, wz = self._check_region(region)
+        f = self.flags[self.gz + z0:self.gz + z0 + wz, self.gy + y0:self.gy + y0 + wy, x0:x0 + wx]
+        return f.contiguous().cpu().numpy().view(ut)
 
     def _interior(self, a):
         nx, ny, nz = self.shape
@@ -999,6 +1004,104 @@ class Lattice:
         self._fields_gen += 1
         self.exchange()
 
+    @contextlib.contextmanager
+    def _quantity_launch(self, window: Tuple[int, int, int, int, int, int]):
+        """the launch descriptor of a quantity-type kernel (quantity, color, gather) over
+        the window (x0, y0, z0, nx, ny, nz) of the local interior: current settings and
+        snapshot, iteration, averaging count, stream; particles attached while the caller
+        launches (quantities may look at them, e.g. Checks), the box reset afterwards"""
+        self._sync_settings()
+        L = self._L
+        L.in_ = self.snaps[self.cur].data_ptr()
+        L.out = self.snaps[1 - self.cur].data_ptr()
+        x0, y0, z0, wx, wy, wz = window
+        L.xlo, L.xhi, L.ylo, L.yhi, L.zlo, L.zhi = x0, x0 + wx, y0, y0 + wy, z0, z0 + wz
+        L.iter = self.iter
+        L.reserved1 = max(1, self.iter - self.average_start)
+        L.stream = self._stream()
+        if self.particles is not None:
+            self.particles.attach_for_quantity(self)
+        try:
+            yield L
+        finally:
+            if self.particles is not None:
+                self.particles.detach(self)
+            nx, ny, nz = self.shape
+            L.reserved0 = 0
+            L.xlo, L.xhi, L.ylo, L.yhi, L.zlo, L.zhi = 0, nx, 0, ny, 0, nz
+
+    def _check_region(self, region) -> Tuple[int, int, int, int, int, int]:
+        """a window (x0, y0, z0, nx, ny, nz) of the local interior (default: all of it)"""
+        nx, ny, nz = self.shape
+        if region is None:
+            return (0, 0, 0, nx, ny, nz)
+        x0, y0, z0, wx, wy, wz = (int(v) for v in region)
+        if (min(x0, y0, z0) < 0 or min(wx, wy, wz) < 0 or x0 + wx > nx or y0 + wy > ny or z0 + wz > nz):
+            raise ValueError(f"region {tuple(region)} is not inside the local interior {self.shape}")
+        return (x0, y0, z0, wx, wy, wz)
+
+    def gather(self, names: Sequence[str], region=None, *, scales: Optional[Sequence[float]] = None,
+               dtype: Optional[torch.dtype] = None, interleave: bool = False) -> Dict[str, torch.Tensor]:
+        """several quantities over one window of the local interior in one node pass (the
+        gather kernel: one pop() per node, every quantity of the plan; core.hpp GatherPlan).
+        region: (x0, y0, z0, nx, ny, nz) in local interior coordinates (default: the whole
+        interior); scales: one factor per name (default 1); dtype: the element type of the
+        result, the compute dtype (default), torch.float32 or torch.float64.  Returns
+        {name: tensor}: scalars (nz, ny, nx), vectors (3, nz, ny, nx) or, interleaved,
+        (nz, ny, nx, 3).  All tensors of a call are views of one device allocation; more than
+        SAMPLE_MAXQ names take more than one launch.  Adjoint quantities (no kernel) are the
+        crop of their full-lattice value in the same layout and dtype."""
+        m = self.model
+        names = list(names)
+        scales = [1.0] * len(names) if scales is None else [float(s) for s in scales]
+        if len(scales) != len(names):
+            raise ValueError("gather: one scale per name")
+        dtype = self.rdtype if dtype is None else dtype
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"gather: dtype {dtype} is neither float32 nor float64")
+        x0, y0, z0, wx, wy, wz = win = self._check_region(region)
+        index = {q.name: i for i, q in enumerate(m.quantities)}
+        entries = []                      # (position in names, quantity index, ncomp, element offset)
+        total = 0
+        for k, name in enumerate(names):
+            if name not in index:
+                raise KeyError(f"model {m.name} has no quantity {name}")
+            q = m.quantities[index[name]]
+            if not q.adjoint:
+                nc = 3 if q.vector else 1
+                entries.append((k, index[name], nc, total))
+                total += nc * wx * wy * wz
+        buf = torch.empty(total, dtype=dtype, device=self.device)
+        es = buf.element_size()
+        nodes = wx * wy * wz
+        res: List[Optional[torch.Tensor]] = [None] * len(names)
+        plans = []
+        for b in range(0, len(entries), abi.SAMPLE_MAXQ):
+            P = abi.GatherPlan()
+            part = entries[b:b + abi.SAMPLE_MAXQ]
+            P.nq = len(part)
+            for i, (k, qi, nc, off) in enumerate(part):
+                P.q[i], P.ncomp[i], P.scale[i] = qi, nc, scales[k]
+                P.otype[i] = abi.GATHER_F32 if dtype == torch.float32 else abi.GATHER_F64
+                P.out[i] = buf.data_ptr() + off * es
+                il = interleave and nc > 1
+                P.cs[i], P.sx[i] = (1, nc) if il else (nodes, 1)
+                P.sy[i], P.sz[i] = P.sx[i] * wx, P.sx[i] * wx * wy
+                v = buf[off:off + nc * nodes]
+                res[k] = v.view(wz, wy, wx, nc) if il else (v.view(nc, wz, wy, wx) if nc > 1 else v.view(wz, wy, wx))
+            plans.append(P)
+        if plans and nodes > 0:
+            with self._quantity_launch(win) as L:
+                for P in plans:
+                    self.lib.gather(L, self.prec, P)
+        for k, name in enumerate(names):
+            q = m.quantities[index[name]]
+            if q.adjoint:
+                nc = 3 if q.vector else 1
+                a = (self._adjoint_quantity(q, nc) * scales[k])[:, z0:z0 + wz, y0:y0 + wy, x0:x0 + wx].to(dtype)
+                res[k] = (a.permute(1, 2, 3, 0).contiguous() if interleave else a.contiguous()) if nc > 1 else a[0].contiguous()
+        return dict(zip(names, res))
+
     def quantity(self, name: str, scale: float = 1.0) -> torch.Tensor:
         """compute a quantity over the local interior: returns (ncomp, nz, ny, nx)"""
         m = self.model
@@ -1011,29 +1114,15 @@ class Lattice:
         if q.adjoint:
             return self._adjoint_quantity(q, nc) * scale
         out = torch.empty((nc, nz, ny, nx), dtype=self.rdtype, device=self.device)
-        self._sync_settings()
-        L = self._L
-        L.in_ = self.snaps[self.cur].data_ptr()
-        L.out = self.snaps[1 - self.cur].data_ptr()
-        L.aux = out.data_ptr()
-        L.quantity = qi
-        L.qcomp = nx * ny * nz
-        L.qscale = float(scale)
-        L.qsy = nx
-        L.qsz = nx * ny
-        L.reserved0 = nc
-        L.ylo, L.yhi, L.zlo, L.zhi = 0, ny, 0, nz
-        L.iter = self.iter
-        L.reserved1 = max(1, self.iter - self.average_start)
-        L.stream = self._stream()
-        if self.particles is not None:   # quantities may look at particles (e.g. Checks)
-            self.particles.attach_for_quantity(self)
-        try:
+        with self._quantity_launch((0, 0, 0, nx, ny, nz)) as L:
+            L.aux = out.data_ptr()
+            L.quantity = qi
+            L.qcomp = nx * ny * nz
+            L.qscale = float(scale)
+            L.qsy = nx
+            L.qsz = nx * ny
+            L.reserved0 = nc
             self.lib.quantity(L, self.prec)
-        finally:
-            if self.particles is not None:
-                self.particles.detach(self)
-        L.reserved0 = 0
         return out
 
     def color(self, z: Optional[int] = None) -> Optional[torch.Tensor]:
@@ -1049,30 +1138,15 @@ class Lattice:
         if not 0 <= lz < nz:
             return None
         out = torch.empty((2, ny, nx), dtype=self.rdtype, device=self.device)
-        self._sync_settings()
-        L = self._L
-        L.in_ = self.snaps[self.cur].data_ptr()
-        L.out = self.snaps[1 - self.cur].data_ptr()
-        L.aux = out.data_ptr()
-        L.quantity = -1
-        L.qcomp = nx * ny
-        L.qscale = 1.0
-        L.qsy = nx
-        L.qsz = nx * ny
-        L.reserved0 = 2
-        L.ylo, L.yhi, L.zlo, L.zhi = 0, ny, lz, lz + 1
-        L.iter = self.iter
-        L.reserved1 = max(1, self.iter - self.average_start)
-        L.stream = self._stream()
-        if self.particles is not None:
-            self.particles.attach_for_quantity(self)
-        try:
+        with self._quantity_launch((0, 0, lz, nx, ny, 1)) as L:
+            L.aux = out.data_ptr()
+            L.quantity = -1
+            L.qcomp = nx * ny
+            L.qscale = 1.0
+            L.qsy = nx
+            L.qsz = nx * ny
+            L.reserved0 = 2
             self.lib.quantity(L, self.prec)
-        finally:
-            if self.particles is not None:
-                self.particles.detach(self)
-            L.reserved0 = 0
-            L.zlo, L.zhi = 0, nz
         return out.permute(1, 2, 0)
 
     def draw_wall(self, x: int, y: int, z: Optional[int] = None, kind: str = "Wall"):

@@ -107,6 +107,26 @@ class SamplePlan(ctypes.Structure):
     ]
 
 
+GATHER_F64, GATHER_F32 = 0, 1   # core.hpp GatherPlan element types
+
+
+class GatherPlan(ctypes.Structure):
+    """mirror of tclb::GatherPlan (csrc/include/tclb/core.hpp): the box plan of
+    Lattice.gather, element strides per entry"""
+    _fields_ = [
+        ("nq", ctypes.c_int), ("reserved", ctypes.c_int),
+        ("q", ctypes.c_int * SAMPLE_MAXQ),
+        ("ncomp", ctypes.c_int * SAMPLE_MAXQ),
+        ("otype", ctypes.c_int * SAMPLE_MAXQ),
+        ("scale", ctypes.c_double * SAMPLE_MAXQ),
+        ("out", ctypes.c_void_p * SAMPLE_MAXQ),
+        ("cs", ctypes.c_longlong * SAMPLE_MAXQ),
+        ("sx", ctypes.c_longlong * SAMPLE_MAXQ),
+        ("sy", ctypes.c_longlong * SAMPLE_MAXQ),
+        ("sz", ctypes.c_longlong * SAMPLE_MAXQ),
+    ]
+
+
 class AdCtx(ctypes.Structure):
     """mirror of tclb::AdCtx (csrc/include/tclb/ad.hpp)"""
     _fields_ = [
@@ -196,6 +216,12 @@ class ModelLib:
         sp = getattr(self.lib, f"tclb_{model}_sizeof_sample_plan")()
         if sp != ctypes.sizeof(SamplePlan):
             raise KernelError(f"ABI mismatch for {path}: sizeof(SamplePlan) {sp} != {ctypes.sizeof(SamplePlan)}")
+        gp = getattr(self.lib, f"tclb_{model}_sizeof_gather_plan")()
+        if gp != ctypes.sizeof(GatherPlan):
+            raise KernelError(f"ABI mismatch for {path}: sizeof(GatherPlan) {gp} != {ctypes.sizeof(GatherPlan)}")
+        self._gat = getattr(self.lib, f"tclb_{model}_gather")
+        self._gat.argtypes = [ctypes.POINTER(Launch), ctypes.c_int, ctypes.POINTER(GatherPlan)]
+        self._gat.restype = ctypes.c_int
         self._it = getattr(self.lib, f"tclb_{model}_iterate")
         self._it.argtypes = [ctypes.POINTER(Launch), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                              ctypes.c_int, ctypes.c_int, ctypes.POINTER(SamplePlan)]
@@ -221,6 +247,12 @@ class ModelLib:
         r = self._smp(ctypes.byref(L), prec, ctypes.byref(plan))
         if r != 0:
             raise KernelError(f"{self.model}[{self.kind}] sample failed: code {r}")
+
+    def gather(self, L: Launch, prec: int, plan: GatherPlan):
+        """every quantity of the plan over the window L.xlo..zhi in one node pass"""
+        r = self._gat(ctypes.byref(L), prec, ctypes.byref(plan))
+        if r != 0:
+            raise KernelError(f"{self.model}[{self.kind}] gather failed: code {r}")
 
     def run(self, L: Launch, prec: int):
         r = self._run(ctypes.byref(L), prec)

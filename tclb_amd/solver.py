@@ -211,13 +211,24 @@ class Solver:
         v = self.units.unit_scale(q.unit)
         return self.lattice.quantity(name, scale=1.0 / v).cpu().numpy()
 
-    def output_fields(self, what: Optional[Sequence[str]]):
-        """(name, array (nz,ny,nx) or (3,nz,ny,nx), ncomp) of the selected flag groups and
-        quantities (SI units) on this rank's slab (reference vtkWriteLattice selection)"""
+    def output_fields(self, what: Optional[Sequence[str]], region=None, dtype=None):
+        """the selected flag groups and quantities (SI units) over the part of the output
+        `region` (global (x0, y0, z0, nx, ny, nz), default the whole lattice) inside this
+        rank's box (reference vtkWriteLattice selection): (lreg, fields) with lreg the
+        global box of that part, or None when the rank holds none of the region, and fields
+        a list of (name, array, ncomp), arrays already cropped to lreg — scalars
+        (nz, ny, nx), vectors interleaved (nz, ny, nx, 3); of size 0 on a rank without a
+        part.  One fused gather evaluates every quantity in one pass over the nodes of
+        lreg, one cropped copy brings the flags; dtype: element type of the quantities
+        (default the compute type)."""
         lat = self.lattice
         allq = what is None or "all" in what
+        sx, sy, sz = lat.slab.offset
+        lreg = _intersect((sx, sy, sz) + tuple(lat.shape), region or self.total)
+        x0, y0, z0, nx, ny, nz = lreg or (sx, sy, sz, 0, 0, 0)
+        local = (x0 - sx, y0 - sy, z0 - sz, nx, ny, nz)
         fields = []
-        flags = lat.get_flags()
+        flags = lat.get_flags(local)
         if what is not None and "flag" in what:
             fields.append(("flag", flags.astype(np.uint16 if self.model.flag_bits == 16 else np.uint32), 1))
         for gname in sorted(self.model.group_masks):
@@ -228,14 +239,12 @@ class Solver:
                 mask = self.model.group_masks[gname]
                 shift = self.model.group_shift.get(gname, 0)
                 fields.append((gname, ((flags & mask) >> shift).astype(np.uint8), 1))
-        for q in self.model.quantities:
-            if allq or (what is not None and q.name in what):
-                a = self.quantity_si(q.name)
-                if q.vector:
-                    fields.append((q.name, a, 3))
-                else:
-                    fields.append((q.name, a[0], 1))
-        return fields
+        qs = [q for q in self.model.quantities if allq or (what is not None and q.name in what)]
+        got = lat.gather([q.name for q in qs], local, scales=[1.0 / self.units.unit_scale(q.unit) for q in qs],
+                         dtype=dtype, interleave=True)
+        for q in qs:
+            fields.append((q.name, got[q.name].cpu().numpy(), 3 if q.vector else 1))
+        return lreg, fields
 
     def write_frame(self, name: str = "Graphics", z: Optional[int] = None) -> str:
         """colour frame of a z slice as PNG (io/render.py; the headless counterpart of the
@@ -249,21 +258,15 @@ class Solver:
 
     def write_vtk(self, name: str, what: Optional[Sequence[str]], region=None):
         from .io import vtk
-        lat = self.lattice
         fn = self.out_iter_file(name, ".vti")
         log.output(f"{self.iter:8d} it writing vtk {fn}")
-        fields = self.output_fields(what)
-        sx, sy, sz = lat.slab.offset
-        nx, ny, nz = lat.shape
-        reg = (sx, sy, sz, nx, ny, nz)
         region = region or self.total
-        sub = _crop(fields, reg, region)
+        lreg, fields = self.output_fields(what, region)
         spacing = 1.0 / self.units.alt("1m") if self.units.alt("1m") != 0 else 1.0
-        if sub is not None:
-            lreg, lfields = sub
-            vtk.write_vti(fn, region, lreg, lfields, spacing=spacing)
-        regs = self.comm.gather_objects(sub[0] if sub is not None else None)
-        names = self.comm.gather_objects(os.path.basename(fn) if sub is not None else None)
+        if lreg is not None:
+            vtk.write_vti(fn, region, lreg, fields, spacing=spacing, interleaved=True)
+        regs = self.comm.gather_objects(lreg)
+        names = self.comm.gather_objects(os.path.basename(fn) if lreg is not None else None)
         if self.rank == 0:
             pieces = [(r, n) for r, n in zip(regs, names) if r is not None]
             meta = [(nme, vtk._VTK_T[np.asarray(a).dtype], nc) for nme, a, nc in fields]
@@ -284,16 +287,14 @@ class Solver:
         contiguous datasets, every rank pwrite()s its slab rows.  hdf5=False writes the
         same blocks as one raw binary file instead."""
         from .io import xdmf
-        lat = self.lattice
-        fields = self.output_fields(what)
         region = region or self.total
-        sx, sy, sz = lat.slab.offset
-        nx, ny, nz = lat.shape
-        sub = _crop(fields, (sx, sy, sz, nx, ny, nz), region)
+        dt = np.float64 if double else np.float32
+        # the quantities come from the gather in the element type of the file
+        lreg, fields = self.output_fields(what, region, dtype=torch.float64 if double else torch.float32)
+        sub = (lreg, fields) if lreg is not None else None
         # one collective file per step, as the reference's outIterCollectiveFile(nm, ".h5")
         base = self.out_iter_collective_file(name, "")
         spacing = 1.0 / self.units.alt("1m") if self.units.alt("1m") != 0 else 1.0
-        dt = np.float64 if double else np.float32
         meta = [(n, (np.dtype(dt) if np.asarray(a).dtype.kind == "f" else np.asarray(a).dtype), nc)
                 for n, a, nc in fields]
         layout = xdmf.layout(region, meta)
@@ -317,10 +318,10 @@ class Solver:
             xdmf.create(data, layout)
         if not (hdf5 and chunk is not None):
             self.comm.barrier()
-            if sub is not None:
-                lreg, lfields = sub
+            if lreg is not None:
                 xdmf.write_piece(data, region, lreg, [(n, np.asarray(a).astype(t, copy=False), nc)
-                                                    for (n, a, nc), (_, t, _) in zip(lfields, meta)], layout)
+                                                    for (n, a, nc), (_, t, _) in zip(fields, meta)], layout,
+                                 interleaved=True)
         self.comm.barrier()
         if self.rank == 0 and (write_xdmf or not hdf5):
             xdmf.write_xmf(base + ".xmf", os.path.basename(data), region, layout, spacing,
@@ -331,7 +332,8 @@ class Solver:
     def _write_h5_chunked(self, data: str, region, sub, meta, chunk, level: int):
         """chunked (and deflated) HDF5 datasets: each rank packs the chunks of its block,
         rank 0 writes the metadata from the gathered chunk lists, each rank writes its
-        chunks (one run per dataset) at the addresses rank 0 hands out"""
+        chunks (one run per dataset) at the addresses rank 0 hands out.  sub: (lreg, fields)
+        of output_fields (vectors interleaved), None on a rank without a part"""
         from .ops.host import h5_chunk_pack, h5_create_chunked
         X0, Y0, Z0, rnx, rny, rnz = region
         blobs, info = [], None
@@ -339,10 +341,7 @@ class Solver:
             (x0, y0, z0, _, _, _), lfields = sub
             info = []
             for (n, a, nc), (_, t, _) in zip(lfields, meta):
-                a = np.asarray(a)
-                if nc > 1:
-                    a = np.moveaxis(a, 0, -1)                # (nz, ny, nx, nc)
-                a = np.ascontiguousarray(a.astype(np.dtype(t).newbyteorder("<"), copy=False))
+                a = np.ascontiguousarray(np.asarray(a).astype(np.dtype(t).newbyteorder("<"), copy=False))
                 cd = tuple(chunk) + ((nc,) if nc > 1 else ())
                 blob, sizes = h5_chunk_pack(a, cd, level)
                 grid = [a.shape[k] // cd[k] for k in range(a.ndim)]
@@ -454,8 +453,8 @@ class Solver:
         load_state(self, path, comp=comp)
 
 
-def _crop(fields, reg, region):
-    """crop local arrays (covering reg) to the output region; returns (lreg, fields)"""
+def _intersect(reg, region):
+    """the part of the box reg inside region (both (x0, y0, z0, nx, ny, nz)), None if empty"""
     x0, y0, z0, nx, ny, nz = reg
     X0, Y0, Z0, NX, NY, NZ = region
     a0, a1 = max(x0, X0), min(x0 + nx, X0 + NX)
@@ -463,10 +462,4 @@ def _crop(fields, reg, region):
     c0, c1 = max(z0, Z0), min(z0 + nz, Z0 + NZ)
     if a1 <= a0 or b1 <= b0 or c1 <= c0:
         return None
-    out = []
-    for name, a, nc in fields:
-        if nc > 1:
-            out.append((name, a[:, c0 - z0:c1 - z0, b0 - y0:b1 - y0, a0 - x0:a1 - x0], nc))
-        else:
-            out.append((name, a[c0 - z0:c1 - z0, b0 - y0:b1 - y0, a0 - x0:a1 - x0], nc))
-    return (a0, b0, c0, a1 - a0, b1 - b0, c1 - c0), out
+    return (a0, b0, c0, a1 - a0, b1 - b0, c1 - c0)
