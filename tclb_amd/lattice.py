@@ -951,6 +951,19 @@ class Lattice:
         f = self.flags[self.gz + z0:self.gz + z0 + wz, self.gy + y0:self.gy + y0 + wy, x0:x0 + wx]
         return f.contiguous().cpu().numpy().view(ut)
 
+    def flag_groups(self, pairs, region=None) -> List[torch.Tensor]:
+        """[((flags & mask) >> shift) as uint8 for (mask, shift) in pairs] over a window of
+        the local interior (region as for gather; flags read as unsigned): contiguous
+        (nz, ny, nx) tensors on the lattice's device.  On the GPU one pass over the window
+        produces every group (ops.device.flag_groups, k_flag_groups)."""
+        x0, y0, z0, wx, wy, wz = self._check_region(region)
+        f = self.flags[self.gz + z0:self.gz + z0 + wz, self.gy + y0:self.gy + y0 + wy, x0:x0 + wx]
+        if self.is_gpu:
+            from .ops import device as D
+            return D.flag_groups(f, pairs, self._stream())
+        u = f.to(torch.int64) & (0xFFFF if self.model.flag_bits == 16 else 0xFFFFFFFF)
+        return [((u & int(m)) >> int(s)).to(torch.uint8) for m, s in pairs]
+
     def _interior(self, a):
         nx, ny, nz = self.shape
         return a[self.gz:self.gz + nz, self.gy:self.gy + ny, :nx]

@@ -1,5 +1,6 @@
 """ctypes binding of the model-independent HIP runtime kernels (csrc/device/*.hip,
-libtclb_device.so): the per-step particle kernels.  On a GPU the library must be there
+libtclb_device.so): the per-step particle kernels, the snapshot allocator and the output
+encoders (base64, flag groups).  On a GPU the library must be there
 (built by ``tclb_amd.build``); a missing or stale one is an error, not a silent switch to
 tensor ops."""
 from __future__ import annotations
@@ -46,6 +47,12 @@ def lib():
             L.tclb_snap_alloc.restype = i
             L.tclb_snap_free.argtypes = [P, i]
             L.tclb_snap_free.restype = i
+            L.tclb_enc_b64.argtypes = [P, P, ctypes.c_longlong, P]
+            L.tclb_enc_b64.restype = i
+            L.tclb_enc_flag_groups.argtypes = [P, i, ctypes.c_longlong, ctypes.c_longlong, i, i, i, i,
+                                               ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint),
+                                               ctypes.POINTER(P), P]
+            L.tclb_enc_flag_groups.restype = i
             _lib = L
     return _lib
 
@@ -70,6 +77,61 @@ def rigid_step(P, acc, m, free, n: int, a, periodic: int, period, stream: int):
                                       float(a[0]), float(a[1]), float(a[2]), periodic,
                                       float(period[0]), float(period[1]), float(period[2]), stream),
            "particle integration")
+
+
+def b64encode(src, out=None, stream=None):
+    """base64 (RFC 4648, '=' padding) of the bytes of the contiguous device tensor `src` (any
+    dtype; its first byte 4-byte aligned) as a uint8 device tensor of 4 * ceil(n / 3)
+    characters: a new one, or the front of `out` (uint8, contiguous, 4-byte aligned, long
+    enough), of which the rest stays untouched (csrc/device/encode.hip k_b64).  stream: a
+    raw HIP stream, default the current one of src's device."""
+    import torch
+    if not src.is_cuda or not src.is_contiguous():
+        raise ValueError("b64encode: src must be a contiguous device tensor")
+    n = src.numel() * src.element_size()
+    m = 4 * ((n + 2) // 3)
+    if out is None:
+        out = torch.empty(m, dtype=torch.uint8, device=src.device)
+    elif out.dtype != torch.uint8 or out.device != src.device or not out.is_contiguous() or out.numel() < m:
+        raise ValueError(f"b64encode: out must be a contiguous uint8 tensor of at least {m} bytes on {src.device}")
+    if stream is None:
+        stream = torch.cuda.current_stream(src.device).cuda_stream
+    with torch.cuda.device(src.device):
+        _check(lib().tclb_enc_b64(src.data_ptr(), out.data_ptr(), n, stream), "base64 encoding")
+    return out[:m]
+
+
+FLAG_GROUPS_MAX = 16
+
+
+def flag_groups(flags, pairs, stream=None):
+    """[((flags & mask) >> shift) as uint8 for (mask, shift) in pairs] of the 3-D device
+    tensor `flags` (int16 or int32 read as unsigned; any strides with x contiguous, e.g. a
+    window of Lattice.flags): contiguous arrays of flags' shape, all views of one
+    allocation, from one pass over the window per FLAG_GROUPS_MAX pairs
+    (csrc/device/encode.hip k_flag_groups)"""
+    import torch
+    if not flags.is_cuda or flags.dim() != 3 or flags.dtype not in (torch.int16, torch.int32):
+        raise ValueError("flag_groups: flags must be a 3-D int16 or int32 device tensor")
+    wz, wy, wx = flags.shape
+    if wx > 1 and flags.stride(2) != 1:
+        raise ValueError("flag_groups: the x axis of flags must be contiguous")
+    pairs = [(int(m) & 0xFFFFFFFF, int(s)) for m, s in pairs]
+    total = wz * wy * wx
+    pitch = (total + 3) // 4 * 4                       # every array starts 4-byte aligned
+    buf = torch.empty((len(pairs), pitch), dtype=torch.uint8, device=flags.device)
+    if stream is None:
+        stream = torch.cuda.current_stream(flags.device).cuda_stream
+    UA, PA = ctypes.c_uint * FLAG_GROUPS_MAX, ctypes.c_void_p * FLAG_GROUPS_MAX
+    with torch.cuda.device(flags.device):
+        for k in range(0, len(pairs) if total else 0, FLAG_GROUPS_MAX):
+            part = pairs[k:k + FLAG_GROUPS_MAX]
+            masks, shifts = UA(*[m for m, _ in part]), UA(*[s for _, s in part])
+            outs = PA(*[buf[k + j].data_ptr() for j in range(len(part))])
+            _check(lib().tclb_enc_flag_groups(flags.data_ptr(), 16 if flags.dtype == torch.int16 else 32,
+                                              flags.stride(1), flags.stride(0), wx, wy, wz, len(part), masks,
+                                              shifts, outs, stream), "flag group extraction")
+    return [buf[j, :total].view(wz, wy, wx) for j in range(len(pairs))]
 
 
 SNAP_ALLOC_MODES = {"torch": -1, "hip": 0, "contiguous": 1, "vmm": 2}

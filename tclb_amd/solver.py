@@ -80,6 +80,7 @@ class Solver:
         self.set_output(config.get("output", ""))
         self._meter_t = time.time()
         self._meter_it = 0
+        self._vtk_slots = None   # staging memory of the device VTK encoding, made by the first such write
 
     # ------------------------------------------------------------------ setup
     def read_units(self):
@@ -211,6 +212,30 @@ class Solver:
         v = self.units.unit_scale(q.unit)
         return self.lattice.quantity(name, scale=1.0 / v).cpu().numpy()
 
+    def _output_selection(self, what: Optional[Sequence[str]]):
+        """what an output of `what` holds (reference vtkWriteLattice selection): (whether the
+        raw flag is in it, [(group name, mask, shift)], [quantity]) — the one rule behind
+        output_fields and output_fields_device"""
+        allq = what is None or "all" in what
+        groups = []
+        for gname in sorted(self.model.group_masks):
+            if gname in ("ALL", "NONE"):
+                continue
+            if (allq and gname != "SETTINGZONE" and gname in {n.group for n in self.model.node_types}) or \
+                    (what is not None and gname in what):
+                groups.append((gname, self.model.group_masks[gname], self.model.group_shift.get(gname, 0)))
+        qs = [q for q in self.model.quantities if allq or (what is not None and q.name in what)]
+        return what is not None and "flag" in what, groups, qs
+
+    def _output_window(self, region):
+        """(lreg, local): the part of the global output `region` inside this rank's box
+        (None: no part) and the same window in local interior coordinates (empty then)"""
+        lat = self.lattice
+        sx, sy, sz = lat.slab.offset
+        lreg = _intersect((sx, sy, sz) + tuple(lat.shape), region or self.total)
+        x0, y0, z0, nx, ny, nz = lreg or (sx, sy, sz, 0, 0, 0)
+        return lreg, (x0 - sx, y0 - sy, z0 - sz, nx, ny, nz)
+
     def output_fields(self, what: Optional[Sequence[str]], region=None, dtype=None):
         """the selected flag groups and quantities (SI units) over the part of the output
         `region` (global (x0, y0, z0, nx, ny, nz), default the whole lattice) inside this
@@ -222,28 +247,38 @@ class Solver:
         lreg, one cropped copy brings the flags; dtype: element type of the quantities
         (default the compute type)."""
         lat = self.lattice
-        allq = what is None or "all" in what
-        sx, sy, sz = lat.slab.offset
-        lreg = _intersect((sx, sy, sz) + tuple(lat.shape), region or self.total)
-        x0, y0, z0, nx, ny, nz = lreg or (sx, sy, sz, 0, 0, 0)
-        local = (x0 - sx, y0 - sy, z0 - sz, nx, ny, nz)
+        want_flag, groups, qs = self._output_selection(what)
+        lreg, local = self._output_window(region)
         fields = []
         flags = lat.get_flags(local)
-        if what is not None and "flag" in what:
+        if want_flag:
             fields.append(("flag", flags.astype(np.uint16 if self.model.flag_bits == 16 else np.uint32), 1))
-        for gname in sorted(self.model.group_masks):
-            if gname in ("ALL", "NONE"):
-                continue
-            if (allq and gname != "SETTINGZONE" and gname in {n.group for n in self.model.node_types}) or \
-                    (what is not None and gname in what):
-                mask = self.model.group_masks[gname]
-                shift = self.model.group_shift.get(gname, 0)
-                fields.append((gname, ((flags & mask) >> shift).astype(np.uint8), 1))
-        qs = [q for q in self.model.quantities if allq or (what is not None and q.name in what)]
+        for gname, mask, shift in groups:
+            fields.append((gname, ((flags & mask) >> shift).astype(np.uint8), 1))
         got = lat.gather([q.name for q in qs], local, scales=[1.0 / self.units.unit_scale(q.unit) for q in qs],
                          dtype=dtype, interleave=True)
         for q in qs:
             fields.append((q.name, got[q.name].cpu().numpy(), 3 if q.vector else 1))
+        return lreg, fields
+
+    def output_fields_device(self, what: Optional[Sequence[str]], region=None, dtype=None):
+        """output_fields with the arrays left on the lattice's device as contiguous tensors
+        in the same layout and element types: `flag` the cropped flags as uint16 / uint32,
+        the groups from Lattice.flag_groups (one pass for all of them), the quantities from
+        the same single gather"""
+        lat = self.lattice
+        want_flag, groups, qs = self._output_selection(what)
+        lreg, local = self._output_window(region)
+        x0, y0, z0, nx, ny, nz = local
+        fields = []
+        if want_flag:
+            f = lat.flags[lat.gz + z0:lat.gz + z0 + nz, lat.gy + y0:lat.gy + y0 + ny, x0:x0 + nx].contiguous()
+            fields.append(("flag", f.view(torch.uint16 if self.model.flag_bits == 16 else torch.uint32), 1))
+        arrays = lat.flag_groups([(mask, shift) for _, mask, shift in groups], local)
+        fields += [(gname, a, 1) for (gname, _, _), a in zip(groups, arrays)]
+        got = lat.gather([q.name for q in qs], local, scales=[1.0 / self.units.unit_scale(q.unit) for q in qs],
+                         dtype=dtype, interleave=True)
+        fields += [(q.name, got[q.name], 3 if q.vector else 1) for q in qs]
         return lreg, fields
 
     def write_frame(self, name: str = "Graphics", z: Optional[int] = None) -> str:
@@ -256,20 +291,39 @@ class Solver:
         render.write_png(self.lattice, fn, z)
         return fn
 
-    def write_vtk(self, name: str, what: Optional[Sequence[str]], region=None):
+    def write_vtk(self, name: str, what: Optional[Sequence[str]], region=None, encode: str = "auto",
+                  chunk: Optional[int] = None):
+        """encode: where the payloads become base64 text — "host" (output_fields, the
+        standard library), "device" (output_fields_device, io/vtk.py write_vti_device: the
+        host only writes finished text; chunk: bytes of text per pipeline chunk) or "auto":
+        device on a GPU lattice, host on the CPU.  The environment's TCLB_VTK_ENCODE
+        overrides the argument.  Both write the same bytes."""
         from .io import vtk
+        encode = os.environ.get("TCLB_VTK_ENCODE") or encode
+        if encode not in ("auto", "host", "device"):
+            raise SolverError(f"VTK encode '{encode}' is none of auto, host, device")
+        if encode == "auto":
+            encode = "device" if self.lattice.is_gpu else "host"
+        if encode == "device" and not self.lattice.is_gpu:
+            raise SolverError("VTK encode 'device' needs a lattice on a GPU")
         fn = self.out_iter_file(name, ".vti")
         log.output(f"{self.iter:8d} it writing vtk {fn}")
         region = region or self.total
-        lreg, fields = self.output_fields(what, region)
         spacing = 1.0 / self.units.alt("1m") if self.units.alt("1m") != 0 else 1.0
-        if lreg is not None:
-            vtk.write_vti(fn, region, lreg, fields, spacing=spacing, interleaved=True)
+        if encode == "device":
+            lreg, fields = self.output_fields_device(what, region)
+            if lreg is not None:
+                self._vtk_slots = vtk.write_vti_device(fn, region, lreg, fields, spacing=spacing, chunk=chunk,
+                                                       slots=self._vtk_slots)
+        else:
+            lreg, fields = self.output_fields(what, region)
+            if lreg is not None:
+                vtk.write_vti(fn, region, lreg, fields, spacing=spacing, interleaved=True)
         regs = self.comm.gather_objects(lreg)
         names = self.comm.gather_objects(os.path.basename(fn) if lreg is not None else None)
         if self.rank == 0:
             pieces = [(r, n) for r, n in zip(regs, names) if r is not None]
-            meta = [(nme, vtk._VTK_T[np.asarray(a).dtype], nc) for nme, a, nc in fields]
+            meta = [(nme, vtk.vtk_type(a), nc) for nme, a, nc in fields]
             vtk.write_pvti(fn[:-4] + ".pvti", region, pieces, meta, spacing=spacing)
         return 0
 
