@@ -104,6 +104,11 @@ class Geometry:
         self.flags = np.zeros((len(zs), len(ys), self.gnx), dtype=np.uint32)
         self.zones: Dict[str, int] = {"DefaultZone": 0}
         self.cuts: Optional[np.ndarray] = None
+        # the lattice this geometry is drawn for (set by the Geometry handler before load): on
+        # a GPU, STL surfaces are voxelised there and their cuts go straight into lattice.cuts
+        # (stl.py draw_stl); None: everything on the host, cuts in self.cuts
+        self.lattice = None
+        self.stl_device: Optional[bool] = None    # where this geometry's STL surfaces were voxelised
         self.fg = 0
         self.fg_mask = 0
         self.fg_mode = MODE_OVERWRITE

@@ -1,9 +1,11 @@
 """STL primitive (reference Geometry::loadSTL / transformSTL, src/Geometry.cpp.Rt:397-688).
 Binary STL only; transforms Xrot/Yrot/Zrot, scale, x/y/z; sides in/out (ray parity,
-native) and surface (sub-voxel cuts for interpolated bounce-back, native)."""
+native) and surface (sub-voxel cuts for interpolated bounce-back: the native host library
+or, for a lattice on a GPU, the device kernels of csrc/device/voxel.hip; same bits)."""
 from __future__ import annotations
 
 import math
+import os
 import struct
 
 import numpy as np
@@ -45,6 +47,26 @@ def transform(tri: np.ndarray, node, units) -> np.ndarray:
 D3Q27_DIRS = np.array([[x, y, z] for z in (0, 1, -1) for y in (0, 1, -1) for x in (0, 1, -1)])[1:]
 
 
+def _surface_on_device(geom) -> bool:
+    """where the STL surfaces of `geom` are voxelised: TCLB_STL_VOXELISE = auto | host |
+    device, auto being the device when the geometry is drawn for a lattice on a GPU
+    (Geometry.lattice) and the host otherwise.  Decided at the geometry's first surface; on
+    the device the cuts go into lattice.cuts, replacing those of an earlier geometry as
+    set_cuts does on the host path."""
+    if geom.stl_device is None:
+        mode = os.environ.get("TCLB_STL_VOXELISE") or "auto"
+        if mode not in ("auto", "host", "device"):
+            raise ValueError(f"TCLB_STL_VOXELISE '{mode}' is none of auto, host, device")
+        lat = geom.lattice
+        gpu = lat is not None and lat.is_gpu
+        if mode == "device" and not gpu:
+            raise ValueError("TCLB_STL_VOXELISE 'device' needs a lattice on a GPU")
+        geom.stl_device = gpu and mode != "host"
+        if geom.stl_device:
+            lat.cuts = None
+    return geom.stl_device
+
+
 def draw_stl(geom, reg, node):
     fn = node.get("file")
     if fn is None:
@@ -57,7 +79,19 @@ def draw_stl(geom, reg, node):
     if r.size() == 0:
         return
     box = (r.dx, r.dy, r.dz, r.nx, r.ny, r.nz)
-    if inside_out == 2:
+    if inside_out == 2 and _surface_on_device(geom):
+        import torch
+        from ..ops import device
+        from .geometry import Region
+        lat = geom.lattice
+        with torch.cuda.device(lat.device):
+            cuts, mask, win = device.stl_cuts(tri, box, D3Q27_DIRS, lat._stream())
+            lat.merge_cuts(cuts, win, geom.ys, geom.zs)
+            sel = mask.cpu().numpy().astype(bool)       # the window's mask only
+        r = Region(*win)
+        if r.size() == 0:
+            return
+    elif inside_out == 2:
         cuts, mask = host.stl_cuts(tri, box, D3Q27_DIRS)
         geom.record_cuts(r, cuts)
         sel = mask.astype(bool)

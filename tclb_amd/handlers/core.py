@@ -111,6 +111,7 @@ class GeometryAction(Action):
         sl = lat.slab
         g = Geometry(s.model, lat.gshape, sl.lo, sl.n, sl.axis, lat.g, units=s.units, permissive=s.permissive,
                      yz=(sl.ylo, sl.ny, lat.gy, sl.zlo, sl.nz, lat.gz) if sl.axis == 3 else None)
+        g.lattice = lat      # STL surfaces are voxelised on its GPU, their cuts merged into lat.cuts
         g.load(self.node)
         s.geometry = g
         lat.set_flags(g.flags)

@@ -188,7 +188,8 @@ class Lattice:
         self.turb_t = None
         self.turb_time_wn = 0.0
         self.cuts = None
-        self.particles = None     # ParticleSystem with pre_stage/post_stage/step hooks
+        self.cut_merges = 0       # merge_cuts calls: STL surfaces voxelised on the device
+        self.particles = None    # ParticleSystem with pre_stage/post_stage/step hooks
         self.average_start = 0
         # the native loop of a multi-rank lattice is created with the lattice, so its
         # collective set-up (the RCCL communicator) happens at the same point on every rank
@@ -974,6 +975,22 @@ class Lattice:
         full = np.full((26, self.NZ, self.NY, self.px), 65535, dtype=np.uint16)
         full[:, :, :, :nx] = cuts
         self.cuts = torch.from_numpy(full.view(np.int16)).to(self.device)
+
+    def merge_cuts(self, win: torch.Tensor, window, ys: np.ndarray, zs: np.ndarray):
+        """unsigned min of the device cuts `win` (26, wz, wy, wx) of the global box `window`
+        (x0, y0, z0, wx, wy, wz; ops.device.stl_cuts) into self.cuts, which is created in the
+        layout of set_cuts, all 65535, on first use; ys / zs: global coordinate of every
+        local row / plane, ghosts included (Geometry.ys, Geometry.zs).  GPU lattices only."""
+        if not self.is_gpu:
+            raise ValueError("merge_cuts needs a lattice on a GPU")
+        from .ops import device as D
+        if len(ys) != self.NY or len(zs) != self.NZ:
+            raise ValueError(f"merge_cuts: {len(ys)} x {len(zs)} row coordinates for {self.NY} x {self.NZ} rows")
+        if self.cuts is None:
+            self.cuts = torch.full((26, self.NZ, self.NY, self.px), -1, dtype=torch.int16, device=self.device)
+        ys_t, zs_t = (torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device) for a in (ys, zs))
+        D.cuts_merge(self.cuts, win, window, ys_t, zs_t, self._stream())
+        self.cut_merges += 1
 
     def set_turbulence(self, modes: np.ndarray, time_wn: float = 0.0):
         """synthetic-turbulence modes (n, 7) -> device (Launch.ext[0]); the time wave number

@@ -1,6 +1,6 @@
 """ctypes binding of the model-independent HIP runtime kernels (csrc/device/*.hip,
-libtclb_device.so): the per-step particle kernels, the snapshot allocator and the output
-encoders (base64, flag groups).  On a GPU the library must be there
+libtclb_device.so): the per-step particle kernels, the snapshot allocator, the output
+encoders (base64, flag groups) and the STL surface voxeliser.  On a GPU the library must be there
 (built by ``tclb_amd.build``); a missing or stale one is an error, not a silent switch to
 tensor ops."""
 from __future__ import annotations
@@ -53,6 +53,15 @@ def lib():
                                                ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint),
                                                ctypes.POINTER(P), P]
             L.tclb_enc_flag_groups.restype = i
+            LL = ctypes.c_longlong
+            L.tclb_stl_tmp_bytes.argtypes = [i]
+            L.tclb_stl_tmp_bytes.restype = LL
+            L.tclb_stl_prep.argtypes = [P, i, i, i, i, i, i, i, P, LL, ctypes.POINTER(LL), P]
+            L.tclb_stl_prep.restype = i
+            L.tclb_stl_cuts.argtypes = [P, i, i, i, i, i, i, i, P, P, LL, LL, P, LL, P, P]
+            L.tclb_stl_cuts.restype = i
+            L.tclb_cuts_merge.argtypes = [P, i, i, i, LL, P, LL, i, i, i, i, i, i, P, P, P]
+            L.tclb_cuts_merge.restype = i
             _lib = L
     return _lib
 
@@ -132,6 +141,83 @@ def flag_groups(flags, pairs, stream=None):
                                               flags.stride(1), flags.stride(0), wx, wy, wz, len(part), masks,
                                               shifts, outs, stream), "flag group extraction")
     return [buf[j, :total].view(wz, wy, wx) for j in range(len(pairs))]
+
+
+def stl_cuts(tri, region, dirs, stream=None):
+    """surface voxelisation of the triangles `tri` ((n, 9) float64 host array, lattice
+    coordinates) over the global box `region` (x0, y0, z0, nx, ny, nz) on the current device,
+    bit for bit what ops.host.stl_cuts computes (csrc/device/voxel.hip k_tri_prep, k_stl_cuts).
+    Returns (cuts, mask, window): window = region cut down to the mesh's integer bounding box,
+    as (x0, y0, z0, wx, wy, wz), outside of which no node has a cut; cuts (26, wz, wy, wx) int16
+    holding the uint16 cut of every direction of `dirs` ((26, 3) ints; 65535: none) and mask
+    (wz, wy, wx) uint8, device tensors over the window.  An empty window launches nothing."""
+    import numpy as np
+    import torch
+    tri = np.ascontiguousarray(tri, dtype=np.float64).reshape(-1, 9)
+    dirs = np.ascontiguousarray(dirs, dtype=np.int32)
+    if dirs.shape != (26, 3):
+        raise ValueError("stl_cuts: dirs must be 26 x 3")
+    r0 = np.array([int(v) for v in region[:3]], dtype=np.int64)
+    rn = np.array([int(v) for v in region[3:]], dtype=np.int64)
+    lo, n = r0, np.zeros(3, dtype=np.int64)
+    if len(tri) and rn.min() > 0:
+        if not np.isfinite(tri).all() or np.abs(tri).max() >= 2 ** 30:
+            raise ValueError("stl_cuts: triangle coordinates must be finite and below 2^30")
+        pts = tri.reshape(-1, 3)
+        lo = np.maximum(np.ceil(pts.min(0)).astype(np.int64) - 1, r0)
+        hi = np.minimum(np.floor(pts.max(0)).astype(np.int64) + 1, r0 + rn - 1)
+        n = hi - lo + 1 if (hi >= lo).all() else n
+    x0, y0, z0, wx, wy, wz = window = tuple(int(v) for v in (*lo, *n))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    nodes = wx * wy * wz
+    plane = nodes + (nodes & 1)                     # every direction starts on a dword
+    buf = torch.empty((26, plane), dtype=torch.int16, device=dev)
+    cuts = buf[:, :nodes].view(26, wz, wy, wx)
+    mask = torch.empty((wz, wy, wx), dtype=torch.uint8, device=dev)
+    if nodes == 0:
+        return cuts, mask, window
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    L = lib()
+    tri_d, dirs_d = torch.from_numpy(tri).to(dev), torch.from_numpy(dirs).to(dev)
+    tmp = torch.empty(L.tclb_stl_tmp_bytes(len(tri)), dtype=torch.uint8, device=dev)
+    nchunks = ctypes.c_longlong(0)
+    with torch.cuda.device(dev):
+        _check(L.tclb_stl_prep(tri_d.data_ptr(), len(tri), x0, y0, z0, wx, wy, wz, tmp.data_ptr(), tmp.numel(),
+                               ctypes.byref(nchunks), stream), "STL triangle boxes")
+        _check(L.tclb_stl_cuts(tri_d.data_ptr(), len(tri), x0, y0, z0, wx, wy, wz, dirs_d.data_ptr(),
+                               tmp.data_ptr(), tmp.numel(), nchunks.value, buf.data_ptr(), plane, mask.data_ptr(),
+                               stream), "STL cut distances")
+    return cuts, mask, window
+
+
+def cuts_merge(dst, win, window, ys, zs, stream=None):
+    """dst = min(dst, win), unsigned, where they overlap: dst (26, NZ, NY, px) int16 is a
+    lattice's cut array, whose local row (k, j) lies at global (ys[j], zs[k]) (int32 device
+    tensors; ghost and periodic-wrap rows repeat coordinates); win (26, wz, wy, wx) the cuts
+    of `window` (x0, y0, z0, wx, wy, wz) as stl_cuts returns them
+    (csrc/device/voxel.hip k_cuts_merge)"""
+    import torch
+    x0, y0, z0, wx, wy, wz = (int(v) for v in window)
+    if not dst.is_cuda or dst.dtype != torch.int16 or dst.dim() != 4 or dst.shape[0] != 26 or \
+            not dst.is_contiguous():
+        raise ValueError("cuts_merge: dst must be a contiguous (26, NZ, NY, px) int16 device tensor")
+    if win.device != dst.device or win.dtype != torch.int16 or tuple(win.shape) != (26, wz, wy, wx):
+        raise ValueError(f"cuts_merge: win must be a (26, {wz}, {wy}, {wx}) int16 tensor on {dst.device}")
+    if wx * wy * wz == 0:
+        return
+    if win.stride()[1:] != (wy * wx, wx, 1):
+        raise ValueError("cuts_merge: the planes of win must be contiguous")
+    _, NZ, NY, px = dst.shape
+    for t, n in ((ys, NY), (zs, NZ)):
+        if t.device != dst.device or t.dtype != torch.int32 or t.shape != (n,) or not t.is_contiguous():
+            raise ValueError("cuts_merge: ys / zs must be int32 device tensors of NY / NZ entries")
+    if stream is None:
+        stream = torch.cuda.current_stream(dst.device).cuda_stream
+    with torch.cuda.device(dst.device):
+        _check(lib().tclb_cuts_merge(dst.data_ptr(), NZ, NY, px, dst.stride(0), win.data_ptr(), win.stride(0),
+                                     x0, y0, z0, wx, wy, wz, ys.data_ptr(), zs.data_ptr(), stream),
+               "STL cut merge")
 
 
 SNAP_ALLOC_MODES = {"torch": -1, "hip": 0, "contiguous": 1, "vmm": 2}
