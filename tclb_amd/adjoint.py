@@ -27,8 +27,8 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .lattice import _runs
 from .ops import abi
+from .parallel.halo import runs
 
 
 class AdjointError(RuntimeError):
@@ -372,12 +372,12 @@ class Adjoint:
                 aout = a                 # every field is an output of the stage
             else:
                 aout = torch.zeros_like(a)
-                for r0, r1 in _runs(saved):
+                for r0, r1 in runs(saved):
                     aout[r0:r1] = a[r0:r1]
             ain = self._ad_stage(si, inputs[k], aout, obj_weight)
             if k > 0:
                 keep = a.clone()
-                for r0, r1 in _runs(saved):
+                for r0, r1 in runs(saved):
                     keep[r0:r1] = 0      # written in place: the old values are overwritten
                 a = ain + keep
             else:

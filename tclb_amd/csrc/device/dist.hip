@@ -613,7 +613,6 @@ void* tclb_ipc_open(const void* handle) {
 void tclb_ipc_close(void* p) {
   if (p) (void)hipIpcCloseMemHandle(p);
 }
-int tclb_ipc_handle_bytes() { return (int)sizeof(hipIpcMemHandle_t); }
 
 int tclb_dist_sig_handle(void* ctx, void* out) {
   Ctx* c = (Ctx*)ctx;
@@ -677,18 +676,6 @@ int tclb_loop_iterate(void* ctx, const tclb::Launch* L, int prec, int es, int ns
     if (c->R.async_error(c->comm, &ae) == 0 && ae != 0) return rccl_check(c, ae, "RCCL async error");
   }
   return 0;
-}
-
-// one exchange outside the loop (the Python step path of the same plan)
-int tclb_dist_exchange(void* ctx, void* base, const tclb::HaloOp* ops, int nops, void* stream) {
-  Ctx* c = (Ctx*)ctx;
-  GpuSvc sv{c, (hipStream_t)stream, 0, nullptr, nullptr, 8, 0, 0, 0, 0};
-  tclb::LoopPlan P = {};
-  tclb::StagePlan st = {};
-  P.ops = ops;
-  st.nops = nops;
-  int r = sv.xstart((char*)base, P, st, 1);
-  return r != 0 ? r : sv.xfinish();
 }
 
 // the exchange of stage k of a plan outside the loop (Lattice.exchange on a rank whose

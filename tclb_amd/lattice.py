@@ -29,6 +29,7 @@ import torch
 from .models import registry
 from .models.dsl import Model
 from .ops import abi
+from .parallel import halo
 from .parallel.comm import Comm, LoopbackComm
 from .parallel.decomp import Slab, decompose
 from .parallel.native import NativeLoop, native_dist_enabled
@@ -45,20 +46,6 @@ _SAFE_MATH["max"] = max
 
 def eval_expr(expr: str, env: Dict[str, float]) -> float:
     return float(eval(expr, {"__builtins__": {}}, {**_SAFE_MATH, **env}))
-
-
-FIXED_POINT_SWEEPS = 100   # reference: for (int fix=0; fix<100; fix++), src/Lattice.cu.Rt:484
-
-
-def _runs(idx: Sequence[int]) -> List[Tuple[int, int]]:
-    """contiguous runs [a, b) of a sorted index list"""
-    out = []
-    for i in sorted(idx):
-        if out and out[-1][1] == i:
-            out[-1][1] = i + 1
-        else:
-            out.append([i, i + 1])
-    return [(a, b) for a, b in out]
 
 
 class Lattice:
@@ -172,7 +159,6 @@ class Lattice:
         self.halo_sets = {a: ([i for i, f in enumerate(m.fields) if f.stencil[a][0] < 0],
                               [i for i, f in enumerate(m.fields) if f.stencil[a][1] > 0])
                           for a in ((1, 2) if ax == 3 else (ax,))}
-        self.halo_lo, self.halo_hi = self.halo_sets[2 if ax == 3 else ax]
         self._halo_bufs = {}
         self._dist = None                 # NativeLoop of the native action loop (parallel/native.py)
         # native multi-step loop (ops.abi ModelLib.iterate) for halo-free lattices
@@ -354,7 +340,7 @@ class Lattice:
         """the halo planes of `fields` as one contiguous message: one strided copy for a
         contiguous run of fields, else one gather kernel (index_select)"""
         planes = self._axis_planes(buf, a, b, axis)
-        runs = _runs(fields)
+        runs = halo.runs(fields)
         if len(runs) == 1:
             return planes[runs[0][0]:runs[0][1]].contiguous()
         return planes.index_select(0, self._field_index_t(fields))
@@ -362,7 +348,7 @@ class Lattice:
     def _unpack(self, buf: torch.Tensor, fields: List[int], a: int, b: int, data: torch.Tensor,
                 axis: Optional[int] = None):
         planes = self._axis_planes(buf, a, b, axis)
-        runs = _runs(fields)
+        runs = halo.runs(fields)
         if len(runs) == 1:
             planes[runs[0][0]:runs[0][1]].copy_(data)
         else:
@@ -380,16 +366,13 @@ class Lattice:
         return self._halo_axis_start(buf, fields, self.slab.axis)
 
     def _halo_axis_start(self, buf: torch.Tensor, fields: Optional[Sequence[int]], axis: int):
-        g = self.gz if axis == 2 else self.gy
-        n = self.shape[2] if axis == 2 else self.shape[1]
-        lo_set, hi_set = self.halo_sets[axis]
-        lo = [i for i in lo_set if fields is None or i in fields]
-        hi = [i for i in hi_set if fields is None or i in fields]
+        g, n = halo.axis_extent(self, axis)
+        lo, hi = halo.side_fields(self, axis, fields)
         if not self.comm.distributed:
             # loopback: periodic wrap = plane copies inside this snapshot
-            for r0, r1 in _runs(lo):
+            for r0, r1 in halo.runs(lo):
                 self._axis_planes(buf, 0, g, axis)[r0:r1].copy_(self._axis_planes(buf, n, n + g, axis)[r0:r1])
-            for r0, r1 in _runs(hi):
+            for r0, r1 in halo.runs(hi):
                 self._axis_planes(buf, n + g, n + 2 * g, axis)[r0:r1].copy_(self._axis_planes(buf, g, 2 * g, axis)[r0:r1])
             return None
         if trace.ENABLED:
@@ -407,8 +390,7 @@ class Lattice:
             return
         h, buf, lo, hi, rb, ra, su, sd, axis = st
         self.comm.wait_halo(h)
-        g = self.gz if axis == 2 else self.gy
-        n = self.shape[2] if axis == 2 else self.shape[1]
+        g, n = halo.axis_extent(self, axis)
         if lo:
             self._unpack(buf, lo, 0, g, rb, axis)
         if hi:
@@ -424,7 +406,7 @@ class Lattice:
         key = ("mirror", axis, side, tuple(fields))
         t = self._halo_bufs.get(key)
         if t is None:
-            g = self.gz if axis == 2 else self.gy
+            g, _ = halo.axis_extent(self, axis)
             shape = (len(fields), g, self.NY, self.px) if axis == 2 else (len(fields), self.NZ, g, self.px)
             t = self._halo_bufs[key] = torch.zeros(shape, dtype=self.sdtype, device=self.device)
         return t
@@ -435,20 +417,13 @@ class Lattice:
         buffer `target` (Launch.mbase, core.hpp mirror_store): the border kernel packs the
         outgoing halo itself"""
         L = self._L
-        key = ("slots", tuple(fields))
-        table = self._halo_bufs.get(key)
-        if table is None:
-            vals = [-1] * abi.MIRROR_FIELDS
-            for k, f in enumerate(fields):
-                vals[f] = k
-            table = self._halo_bufs[key] = (ctypes.c_byte * abi.MIRROR_FIELDS)(*vals)
-        L.mslot = table
+        key = ("slots", tuple(fields), rng[0])
+        spec = self._halo_bufs.get(key)
+        if spec is None:
+            *dims, slot = halo.mirror_spec(self, axis, fields, rng[0])
+            spec = self._halo_bufs[key] = (*dims, (ctypes.c_byte * abi.MIRROR_FIELDS)(*slot))
+        L.mfs, L.msy, L.msz, L.moy, L.moz, L.mslot = spec
         L.mbase = target.data_ptr()
-        L.mfs = target.stride(0)
-        if axis == 2:
-            L.msy, L.msz, L.moy, L.moz = self.px, self.NY * self.px, self.gy, -rng[0]
-        else:
-            L.msy, L.msz, L.moy, L.moz = self.px, target.shape[2] * self.px, -rng[0], self.gz
         try:
             self._launch_stage(stage, src, dst, glob, rng)
         finally:
@@ -460,12 +435,8 @@ class Lattice:
         Reference: RunBorder + MPIStream_A (src/Lattice.cu.Rt:466-533), which packs the
         margin blocks on the device in separate copy kernels."""
         axis = self.slab.axis
-        g = self.gz if axis == 2 else self.gy
-        n = self.shape[2] if axis == 2 else self.shape[1]
-        lo_set, hi_set = self.halo_sets[axis]
-        fs = set(fields)
-        lo = [i for i in lo_set if i in fs]        # read from below: my top planes go up
-        hi = [i for i in hi_set if i in fs]        # read from above: my bottom planes go down
+        g, n = halo.axis_extent(self, axis)
+        lo, hi = halo.side_fields(self, axis, fields)
         send_down = self._mirror_buffer(hi, axis, "down") if hi else None
         send_up = self._mirror_buffer(lo, axis, "up") if lo else None
         if hi:
@@ -492,8 +463,8 @@ class Lattice:
         rows over the ghost-inclusive z extent, which fills the edge ghosts) on a side
         stream while the interior kernel runs.  Reference: RunBorder -> MPIStream_A ->
         RunInterior -> MPIStream_B (src/Lattice.cu.Rt:466-533) over MPIDivision's grid."""
-        nx, ny, nz = self.shape
-        gy, gz = self.gy, self.gz
+        gy, ny = halo.axis_extent(self, 1)
+        gz, nz = halo.axis_extent(self, 2)
         for box in ((0, ny, 0, gz), (0, ny, nz - gz, nz), (0, gy, gz, nz - gz), (ny - gy, ny, gz, nz - gz)):
             self._launch_stage(stage, src, dst, glob, box=box)
         if trace.ENABLED:
@@ -536,8 +507,7 @@ class Lattice:
             return
         axes = (1, 2) if self.slab.axis == 3 else (self.slab.axis,)
         for axis in axes:
-            g = self.gz if axis == 2 else self.gy
-            n = self.shape[2] if axis == 2 else self.shape[1]
+            g, n = halo.axis_extent(self, axis)
             if g == 0:
                 continue
             lo_ghost = self._axis_planes(a, 0, g, axis)              # owner: prev rank, its top planes
@@ -578,6 +548,44 @@ class Lattice:
             r = cache[key] = [i for i, f in enumerate(self.model.fields) if self.model.matches(f, stage.save_fields)]
         return r
 
+    def _stage_plain(self, stage: int, src, dst, glob: bool, fields: List[int], mirror: bool):
+        """launch + exchange of one stage in place (dist_loop.hpp loop_stage_plain): the
+        overlapped Y x Z grid step, the overlapped slab step (border launches that pack
+        their halo with `mirror`, else pack kernels after them), or one launch followed by
+        the exchange"""
+        if self.overlap and self.slab.axis == 3:
+            if self.shape[1] > 2 * self.gy and self.shape[2] > 2 * self.gz:
+                return self._grid_overlapped(stage, src, dst, glob, fields)
+        elif self.overlap:
+            g, n = halo.axis_extent(self, self.slab.axis)
+            if n > 2 * g:
+                if mirror:
+                    hs = self._border_mirrored(stage, src, dst, glob, fields)
+                else:
+                    self._launch_stage(stage, src, dst, glob, (0, g))
+                    self._launch_stage(stage, src, dst, glob, (n - g, n))
+                    hs = self._halo_start(dst, fields)
+                self._launch_stage(stage, src, dst, glob, (g, n - g))
+                return self._halo_finish(hs)
+        self._launch_stage(stage, src, dst, glob)
+        self._halo_finish(self._halo_start(dst, fields))
+
+    def _stage_oop(self, stage: int, dst, glob: bool, fields: List[int], sweeps: int):
+        """`sweeps` out-of-place sweeps of one stage (dist_loop.hpp loop_stage_oop): launch
+        into the scratch snapshot, copy the saved fields back, exchange.  One sweep for a
+        stage that reads (through a stencil) a field it also writes, so every node sees the
+        pre-stage values (the reference runs it in place, an order-dependent race;
+        tools/race_check.py finds these).  FIXED_POINT_SWEEPS for a fixed-point stage
+        (reference AddStage(fixedPoint=TRUE), src/Lattice.cu.Rt:484), which the reference
+        also sweeps in place (an order-dependent Gauss-Seidel on the GPU): here every sweep
+        reads the current snapshot, a deterministic Jacobi iteration."""
+        scratch = self._scratch_snapshot()
+        for _ in range(sweeps):
+            self._launch_stage(stage, dst, scratch, glob)
+            for r0, r1 in halo.runs(fields):
+                dst[r0:r1].copy_(scratch[r0:r1])
+            self._halo_finish(self._halo_start(dst, fields))
+
     def run_action(self, name: str, glob: bool = False, reduce: bool = True):
         """one action; with glob the globals are integrated and (reduce) all-reduced and
         copied to the host (reduce=False leaves them on the device: globals_vector())"""
@@ -592,8 +600,6 @@ class Lattice:
         dst = self.snaps[1 - self.cur]
         if glob:
             self.globals_t.zero_()
-        n = self.shape[2] if self.slab.axis == 2 else self.shape[1]
-        g = self.g
         if trace.ENABLED:
             trace.push(f"action {name}")
         for k, sname in enumerate(act.stages):
@@ -605,46 +611,12 @@ class Lattice:
             fields = self._saved_fields(st)
             if st.particle and self.particles is not None:
                 self.particles.pre_stage(self)
-            if st.snapshot_reads and k > 0 and not st.fixed_point:
-                # a stage that reads (through a stencil) a field it also writes: run it
-                # out of place so every node sees the pre-stage values (the reference runs
-                # it in place, an order-dependent race; tools/race_check.py finds these)
-                scratch = self._scratch_snapshot()
-                self._launch_stage(si, dst, scratch, glob)
-                for r0, r1 in _runs(fields):
-                    dst[r0:r1].copy_(scratch[r0:r1])
-                self._halo_finish(self._halo_start(dst, fields))
-            elif st.fixed_point and k > 0:
-                # fixed-point stage (reference AddStage(fixedPoint=TRUE): 100 sweeps,
-                # src/Lattice.cu.Rt:484).  The reference sweeps in place (input == output
-                # snapshot, an order-dependent Gauss-Seidel on the GPU); here every sweep
-                # reads the current snapshot and writes a scratch one whose saved fields
-                # are copied back: a deterministic Jacobi iteration.
-                scratch = self._scratch_snapshot()
-                for _ in range(FIXED_POINT_SWEEPS):
-                    self._launch_stage(si, dst, scratch, glob)
-                    for r0, r1 in _runs(fields):
-                        dst[r0:r1].copy_(scratch[r0:r1])
-                    self._halo_finish(self._halo_start(dst, fields))
-            elif self.overlap and self.slab.axis == 3:
-                if self.shape[1] > 2 * self.gy and self.shape[2] > 2 * self.gz:
-                    self._grid_overlapped(si, inp, dst, glob, fields)
-                else:
-                    self._launch_stage(si, inp, dst, glob)
-                    self._halo_finish(self._halo_start(dst, fields))
-            elif self.overlap and n > 2 * g:
+            mode = halo.stage_mode(k, st)
+            if mode == 0:
                 # a split stage's class-0 nodes store nothing, not even into the mirror
-                if self.halo_mirror and not st.split:
-                    hs = self._border_mirrored(si, inp, dst, glob, fields)
-                else:
-                    self._launch_stage(si, inp, dst, glob, (0, g))
-                    self._launch_stage(si, inp, dst, glob, (n - g, n))
-                    hs = self._halo_start(dst, fields)
-                self._launch_stage(si, inp, dst, glob, (g, n - g))
-                self._halo_finish(hs)
+                self._stage_plain(si, inp, dst, glob, fields, self.halo_mirror and not st.split)
             else:
-                self._launch_stage(si, inp, dst, glob)
-                self._halo_finish(self._halo_start(dst, fields))
+                self._stage_oop(si, dst, glob, fields, halo.FIXED_POINT_SWEEPS if mode == 2 else 1)
             if st.particle and self.particles is not None:
                 self.particles.post_stage(self)
                 if name != "Init":

@@ -49,12 +49,12 @@ import numpy as np
 import torch
 
 from ..ops import abi
+from . import halo
 from .comm import LoopbackComm, TorchDistComm
 
 MAX_STAGES = 32       # dist_loop.hpp DIST_MAX_STAGES
 TAG_HI = 1 << 12      # tag offset of the fields read from above
 TAG_Y = 1 << 13       # tag offset of the grid's y phase
-FIXED_POINT_SWEEPS = 100
 
 
 class HaloOp(ctypes.Structure):
@@ -175,8 +175,6 @@ def _dev_lib():
         L.tclb_ad_segment.restype = i
         L.tclb_loop_exchange.argtypes = [P, P, P, i, i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, i, P]
         L.tclb_loop_exchange.restype = i
-        L.tclb_dist_exchange.argtypes = [P, P, P, i, P]
-        L.tclb_dist_exchange.restype = i
         L.tclb_dist_wait.argtypes = [P, P, i]
         L.tclb_dist_wait.restype = i
         L.tclb_part_tmp_bytes.argtypes = [i, i]
@@ -294,16 +292,6 @@ class IpcMap:
             self.ptr = None
 
 
-def _runs(idx: List[int]) -> List[Tuple[int, int]]:
-    out: List[Tuple[int, int]] = []
-    for i in idx:
-        if out and out[-1][1] == i:
-            out[-1] = (out[-1][0], i + 1)
-        else:
-            out.append((i, i + 1))
-    return out
-
-
 def _carr(ctype, items):
     a = (ctype * max(1, len(items)))()
     for i, it in enumerate(items):
@@ -349,32 +337,6 @@ class NativeLoop:
     def _peers(self, axis: int) -> Tuple[int, int]:
         return self.lat.slab.neighbours(axis) if self.multi else (0, 0)
 
-    def ops_for(self, fields) -> list:
-        """the direct (contiguous plane) halo ops of one stage saving `fields`: along the
-        slab axis, or the z phase of the grid (see dist_loop.hpp for the order)"""
-        lat = self.lat
-        ax = 2 if lat.slab.axis == 3 else lat.slab.axis
-        g = lat.gz if lat.slab.axis == 3 else lat.g
-        n = lat.shape[2] if ax == 2 else lat.shape[1]
-        plane = lat.NY * lat.px if ax == 2 else lat.px
-        es = lat.snaps[0].element_size()
-        prev, nxt = self._peers(ax)
-        fs = set(fields)
-        lo_set, hi_set = lat.halo_sets[ax]
-        lo = [i for i in lo_set if i in fs]        # read from below: my top planes go up
-        hi = [i for i in hi_set if i in fs]        # read from above: my bottom planes go down
-        b = g * plane * es
-        ops = []
-        for f in lo:
-            ops.append(((f * lat.fs + n * plane) * es, b, 0, nxt, f, 0))
-        for f in hi:
-            ops.append(((f * lat.fs + g * plane) * es, b, 0, prev, TAG_HI + f, 0))
-        for f in lo:
-            ops.append((f * lat.fs * es, b, 1, prev, f, 0))
-        for f in hi:
-            ops.append(((f * lat.fs + (n + g) * plane) * es, b, 1, nxt, TAG_HI + f, 0))
-        return ops
-
     def phase_a(self, fields, stg_off: int, k: int = 0, lay=None, peer_off=None):
         """the packed exchange of stage k along the slab axis (or the z phase of the
         grid): ONE message per neighbour and direction.  The border launches mirror their
@@ -389,17 +351,12 @@ class NativeLoop:
         rank shares: send up, send down, receive from below, receive from above.  Returns
         (ops, packs, unpacks, mirrors (lo launch, hi launch), staging bytes)."""
         lat = self.lat
-        grid = lat.slab.axis == 3
-        ax = 2 if grid else lat.slab.axis
-        g = lat.gz if grid else lat.g
-        n = lat.shape[2] if ax == 2 else lat.shape[1]
+        ax = 2 if lat.slab.axis == 3 else lat.slab.axis
+        g, n = halo.axis_extent(lat, ax)
         plane = lat.NY * lat.px if ax == 2 else lat.px
         es = lat.snaps[0].element_size()
         prev, nxt = self._peers(ax)
-        fs = set(fields)
-        lo_set, hi_set = lat.halo_sets[ax]
-        lo = [i for i in lo_set if i in fs]        # read from below: my top planes go up
-        hi = [i for i in hi_set if i in fs]        # read from above: my bottom planes go down
+        lo, hi = halo.side_fields(lat, ax, fields)
         per = g * plane * es
         off = stg_off
         su, off = off, off + per * len(lo)
@@ -434,18 +391,8 @@ class NativeLoop:
             unpacks = [(f * fsb, rb + j * per, per, 1, 0) for j, f in enumerate(lo)] + \
                       [(f * fsb + (n + g) * plane * es, ra + j * per, per, 1, 0) for j, f in enumerate(hi)]
 
-        def mirror(flist, boff, r0):
-            if not flist:
-                return None
-            slot = [-1] * abi.MIRROR_FIELDS
-            for j, f in enumerate(flist):
-                slot[f] = j
-            if ax == 2:
-                spec = (g * plane, lat.px, lat.NY * lat.px, lat.gy, -r0)
-            else:
-                spec = (g * plane, lat.px, g * lat.px, -r0, lat.gz)
-            return (boff,) + spec + (slot,)
-        mirrors = (mirror(hi, sd, 0), mirror(lo, su, n - g))
+        mirrors = tuple((boff,) + halo.mirror_spec(lat, ax, flist, r0) if flist else None
+                        for flist, boff, r0 in ((hi, sd, 0), (lo, su, n - g)))
         return ops, packs, unpacks, mirrors, off - stg_off
 
     def y_phase(self, fields, stg_off: int, k: int = 0, lay=None, peer_off=None):
@@ -455,13 +402,10 @@ class NativeLoop:
         the IPC transport pulls the y neighbours' send messages into its receive buffers
         (dir 3 segments) instead of exchanging them.  Returns (ops, packs, pulls, bytes)"""
         lat = self.lat
-        g, n = lat.gy, lat.shape[1]
+        g, n = halo.axis_extent(lat, 1)
         es = lat.snaps[0].element_size()
         prev, nxt = self._peers(1)
-        fs = set(fields)
-        lo_set, hi_set = lat.halo_sets[1]
-        lo = [i for i in lo_set if i in fs]
-        hi = [i for i in hi_set if i in fs]
+        lo, hi = halo.side_fields(lat, 1, fields)
         per = lat.NZ * g * lat.px * es             # one field's rows
         ops, packs, pulls = [], [], []
         msgs, off = {}, stg_off
@@ -474,7 +418,7 @@ class NativeLoop:
 
         def pk(base, flist, y0, unpack):
             o = base
-            for r0, r1 in _runs(flist):
+            for r0, r1 in halo.runs(flist):
                 packs.append({"boff": o, "field0": r0, "nfield": r1 - r0, "y0": y0, "ny": g, "z0": 0,
                               "nz": lat.NZ, "unpack": unpack})
                 o += per * (r1 - r0)
@@ -500,15 +444,6 @@ class NativeLoop:
             pk(msgs["ra"], hi, n + g, 1)
         return ops, packs, pulls, off - stg_off
 
-    @staticmethod
-    def stage_mode(k: int, st) -> int:
-        """0 plain, 1 out of place (snapshot reads), 2 fixed point (lattice.py run_action)"""
-        if k > 0 and st.fixed_point:
-            return 2
-        if k > 0 and st.snapshot_reads:
-            return 1
-        return 0
-
     def _ipc_ranks(self) -> List[int]:
         """ranks of the IPC peers 0..3: below / above along the slab axis (the grid's z),
         then below / above along the grid's y (-1: none)"""
@@ -532,14 +467,14 @@ class NativeLoop:
         for k, si in enumerate(stages):
             st = m.stages[si]
             fields = lat._saved_fields(st) if field_lists is None else field_lists[k]
-            mode = self.stage_mode(k, st) if field_lists is None else 0
+            mode = halo.stage_mode(k, st) if field_lists is None else 0
             need_scratch |= mode > 0
             S = P.st[k]
-            S.stage, S.mode, S.sweeps = si, mode, FIXED_POINT_SWEEPS if mode == 2 else 1
+            S.stage, S.mode, S.sweeps = si, mode, halo.FIXED_POINT_SWEEPS if mode == 2 else 1
             S.particle = 1 if st.particle and field_lists is None else 0
-            S.run0, S.nruns = len(runs), len(_runs(fields)) if mode > 0 else 0
+            S.run0, S.nruns = len(runs), len(halo.runs(fields)) if mode > 0 else 0
             if mode > 0:
-                runs += _runs(fields)
+                runs += halo.runs(fields)
             S.mir_lo = S.mir_hi = -1
             # a split stage's class-0 nodes store nothing (not even into the mirror): its
             # send buffers are packed from the snapshot instead
@@ -820,18 +755,6 @@ class NativeLoop:
         L = lat._L
         r = _dev_lib().tclb_loop_exchange(self.ctx, buf.data_ptr(), ctypes.byref(P), 0, buf.element_size(),
                                           L.fs, L.sz, L.sy, L.px, stream)
-        if r != 0:
-            raise NativeDistError(f"native halo exchange failed ({r}): {_err()}")
-
-    def exchange(self, buf: torch.Tensor, fields):
-        """one exchange of `fields` of snapshot `buf` through the native transport (GPU)"""
-        ops = self.ops_for(fields)
-        if not ops:
-            return
-        arr = _carr(HaloOp, [dict(zip(_OPF, o)) for o in ops])
-        stream = torch.cuda.current_stream(self.lat.device).cuda_stream
-        r = _dev_lib().tclb_dist_exchange(self.ctx, buf.data_ptr(), ctypes.cast(arr, ctypes.c_void_p), len(ops),
-                                          stream)
         if r != 0:
             raise NativeDistError(f"native halo exchange failed ({r}): {_err()}")
 

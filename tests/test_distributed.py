@@ -52,7 +52,7 @@ def test_ranks_match_single(tmp_path, model, shape, world, overlap, native):
     ("d3q27_pf_velocity_thermo", (16, 8, 12), 2),   # multi-stage, stencil-2 fields
 ])
 def test_native_plan_pairs_by_issue_order(tmp_path, monkeypatch, model, shape, world):
-    """the native loop's halo plan (parallel/native.py ops_for) with sends and receives
+    """the native loop's halo plan (parallel/native.py phase_a) with sends and receives
     paired by issue order per peer, tags ignored — the semantics of RCCL's grouped
     ncclSend/ncclRecv — still equals one rank bit for bit (2 ranks: the two directions go to
     the same peer, so only the plan order keeps them apart)"""
