@@ -108,7 +108,8 @@ class Geometry:
         # a GPU, STL surfaces are voxelised there and their cuts go straight into lattice.cuts
         # (stl.py draw_stl); None: everything on the host, cuts in self.cuts
         self.lattice = None
-        self.stl_device: Optional[bool] = None    # where this geometry's STL surfaces were voxelised
+        self.stl_device: Optional[bool] = None    # where this geometry's STL elements are voxelised
+        self.stl_surfaces = 0                     # surfaces voxelised on the device so far
         self.fg = 0
         self.fg_mask = 0
         self.fg_mode = MODE_OVERWRITE

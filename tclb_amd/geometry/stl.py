@@ -1,7 +1,7 @@
 """STL primitive (reference Geometry::loadSTL / transformSTL, src/Geometry.cpp.Rt:397-688).
-Binary STL only; transforms Xrot/Yrot/Zrot, scale, x/y/z; sides in/out (ray parity,
-native) and surface (sub-voxel cuts for interpolated bounce-back: the native host library
-or, for a lattice on a GPU, the device kernels of csrc/device/voxel.hip; same bits)."""
+Binary STL only; transforms Xrot/Yrot/Zrot, scale, x/y/z; sides in/out (ray parity) and
+surface (sub-voxel cuts for interpolated bounce-back), both by the native host library or,
+for a lattice on a GPU, by the device kernels of csrc/device/voxel.hip; same bits."""
 from __future__ import annotations
 
 import math
@@ -47,12 +47,10 @@ def transform(tri: np.ndarray, node, units) -> np.ndarray:
 D3Q27_DIRS = np.array([[x, y, z] for z in (0, 1, -1) for y in (0, 1, -1) for x in (0, 1, -1)])[1:]
 
 
-def _surface_on_device(geom) -> bool:
-    """where the STL surfaces of `geom` are voxelised: TCLB_STL_VOXELISE = auto | host |
+def _on_device(geom) -> bool:
+    """where the STL elements of `geom` are voxelised: TCLB_STL_VOXELISE = auto | host |
     device, auto being the device when the geometry is drawn for a lattice on a GPU
-    (Geometry.lattice) and the host otherwise.  Decided at the geometry's first surface; on
-    the device the cuts go into lattice.cuts, replacing those of an earlier geometry as
-    set_cuts does on the host path."""
+    (Geometry.lattice) and the host otherwise.  Decided at the geometry's first STL."""
     if geom.stl_device is None:
         mode = os.environ.get("TCLB_STL_VOXELISE") or "auto"
         if mode not in ("auto", "host", "device"):
@@ -62,9 +60,19 @@ def _surface_on_device(geom) -> bool:
         if mode == "device" and not gpu:
             raise ValueError("TCLB_STL_VOXELISE 'device' needs a lattice on a GPU")
         geom.stl_device = gpu and mode != "host"
-        if geom.stl_device:
-            lat.cuts = None
     return geom.stl_device
+
+
+def _surface_on_device(geom) -> bool:
+    """_on_device for a surface: on the device the cuts go into lattice.cuts, and the
+    geometry's first surface replaces those of an earlier geometry as set_cuts does on the
+    host path.  A fill never touches them."""
+    if not _on_device(geom):
+        return False
+    if geom.stl_surfaces == 0:
+        geom.lattice.cuts = None
+    geom.stl_surfaces += 1
+    return True
 
 
 def draw_stl(geom, reg, node):
@@ -95,6 +103,25 @@ def draw_stl(geom, reg, node):
         cuts, mask = host.stl_cuts(tri, box, D3Q27_DIRS)
         geom.record_cuts(r, cuts)
         sel = mask.astype(bool)
+    elif _on_device(geom):
+        import torch
+        from ..ops import device
+        from .geometry import Region
+        lat = geom.lattice
+        with torch.cuda.device(lat.device):
+            lev, win = device.stl_fill(tri, box, axis, inside_out, lat._stream())
+            odd = (lev.cpu().numpy() & 1).astype(bool)     # the window's levels only
+        lat.stl_fills += 1
+        w = Region(*win)
+        if inside_out == 0:
+            # outside the window nothing is selected: paint the window alone
+            r, sel = w, odd
+            if r.size() == 0:
+                return
+        else:
+            sel = np.ones((r.nz, r.ny, r.nx), dtype=bool)
+            X, Y, Z = w.dx - r.dx, w.dy - r.dy, w.dz - r.dz
+            sel[Z:Z + w.nz, Y:Y + w.ny, X:X + w.nx] = odd
     else:
         lev = host.stl_fill(tri, box, axis, inside_out)
         sel = (lev % 2) == 1

@@ -175,6 +175,7 @@ class Lattice:
         self.turb_time_wn = 0.0
         self.cuts = None
         self.cut_merges = 0       # merge_cuts calls: STL surfaces voxelised on the device
+        self.stl_fills = 0        # STL bodies (side in / out) voxelised on the device
         self.particles = None    # ParticleSystem with pre_stage/post_stage/step hooks
         self.average_start = 0
         # the native loop of a multi-rank lattice is created with the lattice, so its

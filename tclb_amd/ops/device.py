@@ -1,6 +1,6 @@
 """ctypes binding of the model-independent HIP runtime kernels (csrc/device/*.hip,
 libtclb_device.so): the per-step particle kernels, the snapshot allocator, the output
-encoders (base64, flag groups) and the STL surface voxeliser.  On a GPU the library must be there
+encoders (base64, flag groups) and the STL voxelisers (surface cuts, ray fill).  On a GPU the library must be there
 (built by ``tclb_amd.build``); a missing or stale one is an error, not a silent switch to
 tensor ops."""
 from __future__ import annotations
@@ -60,6 +60,10 @@ def lib():
             L.tclb_stl_prep.restype = i
             L.tclb_stl_cuts.argtypes = [P, i, i, i, i, i, i, i, P, P, LL, LL, P, LL, P, P]
             L.tclb_stl_cuts.restype = i
+            L.tclb_stl_prep_rays.argtypes = [P, i, i, i, i, i, i, i, i, P, LL, ctypes.POINTER(LL), P]
+            L.tclb_stl_prep_rays.restype = i
+            L.tclb_stl_ray_fill.argtypes = [P, i, i, i, i, i, i, i, i, i, i, P, LL, LL, P, LL, P, P]
+            L.tclb_stl_ray_fill.restype = i
             L.tclb_cuts_merge.argtypes = [P, i, i, i, LL, P, LL, i, i, i, i, i, i, P, P, P]
             L.tclb_cuts_merge.restype = i
             _lib = L
@@ -143,6 +147,76 @@ def flag_groups(flags, pairs, stream=None):
     return [buf[j, :total].view(wz, wy, wx) for j in range(len(pairs))]
 
 
+def _stl_box(tri, region, what: str):
+    """(tri as a contiguous (n, 9) float64 array, origin and size of `region`, the mesh's integer
+    bounding box (ceil(min) - 1, floor(max) + 1) or None without triangles or nodes)"""
+    import numpy as np
+    tri = np.ascontiguousarray(tri, dtype=np.float64).reshape(-1, 9)
+    r0 = np.array([int(v) for v in region[:3]], dtype=np.int64)
+    rn = np.array([int(v) for v in region[3:]], dtype=np.int64)
+    if not len(tri) or rn.min() <= 0:
+        return tri, r0, rn, None
+    # per-axis extrema over contiguous rows (a reduction over the 3-wide axis is ten times slower);
+    # NaN propagates through min and max, so the six numbers also carry the finiteness check
+    xyz = np.ascontiguousarray(tri.reshape(-1, 3).T)
+    mn, mx = xyz.min(1), xyz.max(1)
+    if not (np.isfinite(mn).all() and np.isfinite(mx).all()) or max(-mn.min(), mx.max()) >= 2 ** 30:
+        raise ValueError(f"{what}: triangle coordinates must be finite and below 2^30")
+    return tri, r0, rn, (np.ceil(mn).astype(np.int64) - 1, np.floor(mx).astype(np.int64) + 1)
+
+
+def stl_fill(tri, region, axis: int, inside_out: int, stream=None):
+    """ray-parity levels of the solid body bounded by the triangles `tri` ((n, 9) float64 host
+    array, lattice coordinates) over the global box `region` (x0, y0, z0, nx, ny, nz) on the
+    current device, rays along `axis` (0, 1, 2), bit for bit what ops.host.stl_fill computes
+    (csrc/device/voxel.hip k_tri_prep, k_stl_hits, k_ray_rows / k_ray_x).  Returns (lev, window):
+    lev (wz, wy, wx) uint8 device tensor, inside_out (0, 1) + the number of surface crossings
+    at or above the node, mod 256 (odd: inside); window = (x0, y0, z0, wx, wy, wz), the region
+    cut down to the mesh's integer bounding box across the rays and to region bottom ...
+    min(mesh top, region top) along them, outside of which every node of the region has
+    lev = inside_out.  An empty window launches nothing."""
+    import numpy as np
+    import torch
+    axis, inside_out = int(axis), int(inside_out)
+    if axis not in (0, 1, 2) or inside_out not in (0, 1):
+        raise ValueError("stl_fill: axis must be 0, 1 or 2 and inside_out 0 or 1")
+    tri, r0, rn, box = _stl_box(tri, region, "stl_fill")
+    lo, n, cb = r0, np.zeros(3, dtype=np.int64), 0
+    if box is not None:
+        lo = np.maximum(box[0], r0)
+        hi = np.minimum(box[1], r0 + rn - 1)
+        lo[axis] = r0[axis]
+        if (hi >= lo).all():
+            n = hi - lo + 1
+            # counters from the mesh's lowest box cell up; a mesh wholly above the window
+            # counts at its top
+            cb = int(min(max(box[0][axis], r0[axis]), hi[axis]))
+        else:
+            lo = r0
+    x0, y0, z0, wx, wy, wz = window = tuple(int(v) for v in (*lo, *n))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    lev = torch.empty((wz, wy, wx), dtype=torch.uint8, device=dev)
+    nodes = wx * wy * wz
+    if nodes == 0:
+        return lev, window
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    L = lib()
+    nray = window[3 + axis]
+    cells = nodes // nray * (window[axis] + nray - cb)
+    tri_d = torch.from_numpy(tri).to(dev)
+    tmp = torch.empty(L.tclb_stl_tmp_bytes(len(tri)), dtype=torch.uint8, device=dev)
+    cnt = torch.empty(cells, dtype=torch.int32, device=dev)
+    nchunks = ctypes.c_longlong(0)
+    with torch.cuda.device(dev):
+        _check(L.tclb_stl_prep_rays(tri_d.data_ptr(), len(tri), x0, y0, z0, wx, wy, wz, axis, tmp.data_ptr(),
+                                    tmp.numel(), ctypes.byref(nchunks), stream), "STL ray columns")
+        _check(L.tclb_stl_ray_fill(tri_d.data_ptr(), len(tri), x0, y0, z0, wx, wy, wz, axis, inside_out, cb,
+                                   tmp.data_ptr(), tmp.numel(), nchunks.value, cnt.data_ptr(), 4 * cells,
+                                   lev.data_ptr(), stream), "STL ray fill")
+    return lev, window
+
+
 def stl_cuts(tri, region, dirs, stream=None):
     """surface voxelisation of the triangles `tri` ((n, 9) float64 host array, lattice
     coordinates) over the global box `region` (x0, y0, z0, nx, ny, nz) on the current device,
@@ -153,19 +227,14 @@ def stl_cuts(tri, region, dirs, stream=None):
     (wz, wy, wx) uint8, device tensors over the window.  An empty window launches nothing."""
     import numpy as np
     import torch
-    tri = np.ascontiguousarray(tri, dtype=np.float64).reshape(-1, 9)
     dirs = np.ascontiguousarray(dirs, dtype=np.int32)
     if dirs.shape != (26, 3):
         raise ValueError("stl_cuts: dirs must be 26 x 3")
-    r0 = np.array([int(v) for v in region[:3]], dtype=np.int64)
-    rn = np.array([int(v) for v in region[3:]], dtype=np.int64)
+    tri, r0, rn, box = _stl_box(tri, region, "stl_cuts")
     lo, n = r0, np.zeros(3, dtype=np.int64)
-    if len(tri) and rn.min() > 0:
-        if not np.isfinite(tri).all() or np.abs(tri).max() >= 2 ** 30:
-            raise ValueError("stl_cuts: triangle coordinates must be finite and below 2^30")
-        pts = tri.reshape(-1, 3)
-        lo = np.maximum(np.ceil(pts.min(0)).astype(np.int64) - 1, r0)
-        hi = np.minimum(np.floor(pts.max(0)).astype(np.int64) + 1, r0 + rn - 1)
+    if box is not None:
+        lo = np.maximum(box[0], r0)
+        hi = np.minimum(box[1], r0 + rn - 1)
         n = hi - lo + 1 if (hi >= lo).all() else n
     x0, y0, z0, wx, wy, wz = window = tuple(int(v) for v in (*lo, *n))
     dev = torch.device("cuda", torch.cuda.current_device())
