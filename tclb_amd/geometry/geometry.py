@@ -10,14 +10,18 @@ and the primitives Box, HalfSphere, Sphere, OffgridSphere, OffgridPipe, XPipe,
 YPipe, ZPipe, XAnnulus, Pipe, PipeY, PipeZ, Cylinder, Wedge, STL, Sweep, Text
 (src/Geometry.cpp.Rt:758-1124).
 
-Each primitive is evaluated vectorised over its bounding box only (numpy); the
-STL voxeliser (ray parity + sub-voxel cuts) runs in the native host library.
+Each primitive yields a spec (kind, opt, doubles).  On the host it is evaluated vectorised
+over its bounding box only (numpy); for a lattice on a GPU the specs are collected as a
+display list and rasterised there by k_paint (csrc/device/paint.hip, ops.device.paint), bit
+for bit the same flags (TCLB_GEOMETRY = auto | host | device).  The STL voxeliser (ray
+parity + sub-voxel cuts) runs in the native host library or on the device (stl.py).
 The rank-local array covers the local slab plus its ghost planes (global
 coordinates wrap periodically there), so ghost flags need no exchange.
 """
 from __future__ import annotations
 
 import math
+import os
 import xml.etree.ElementTree as ET
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
@@ -77,7 +81,14 @@ class Geometry:
 
     ``flags``: uint32 array (NZ, NY, nx) = local slab incl. ghost planes; ``gz`` (or
     ``gy``) ghost planes on the decomposed axis; global coordinates of local index
-    k along that axis are ``(lo - g + k) mod n_global``."""
+    k along that axis are ``(lo - g + k) mod n_global``.
+
+    Painting on the device (``on_device()``: TCLB_GEOMETRY, a ``lattice`` on a GPU): ``paint``
+    appends a record instead of painting; the records go through one k_paint launch at the
+    end of ``load``, before anything that paints on the host (Text, an STL voxelised there)
+    and whenever ``paint_batch`` of them are pending.  After ``load`` ``flags`` is the
+    downloaded array, ``device_flags()`` its twin on the GPU, and ``device_paints`` the
+    number of launches (0 on the host path)."""
 
     def __init__(self, model, gshape: Tuple[int, int, int], slab_lo: int, slab_n: int, axis: int, ghost: int,
                  units: Optional[UnitEnv] = None, permissive: bool = False, yz: Optional[Tuple[int, ...]] = None):
@@ -110,6 +121,15 @@ class Geometry:
         self.lattice = None
         self.stl_device: Optional[bool] = None    # where this geometry's STL elements are voxelised
         self.stl_surfaces = 0                     # surfaces voxelised on the device so far
+        # device painting (on_device): primitives are collected as records and rasterised by
+        # ops.device.paint into flags_device, the int32 twin of flags on the lattice's GPU
+        self.paint_device: Optional[bool] = None  # where this geometry is painted
+        self.paint_batch = 4096                   # records that trigger a launch
+        self.device_paints = 0                    # k_paint launches so far (0 on the host path)
+        self.flags_device = None
+        self._device_current = False              # flags_device holds the latest flags
+        self._batch: list = []
+        self._rows = None                         # (ys, zs) on the device
         self.fg = 0
         self.fg_mask = 0
         self.fg_mode = MODE_OVERWRITE
@@ -255,19 +275,96 @@ class Geometry:
         Z = self.zs[zi].astype(np.float64)[:, None, None]
         return X, Y, Z
 
-    def paint(self, r: Region, pred=None):
-        """paint nodes of region r (global coords, clipped) where pred(X,Y,Z) holds"""
+    def paint(self, r: Region, spec=None):
+        """paint nodes of region r (global coords, clipped) where the primitive `spec` holds:
+        None (the whole box), a spec (kind, opt, doubles) or, for what is painted on the host
+        only (Text, an STL voxelised there), a predicate pred(X, Y, Z).  On the device a spec
+        becomes a record of the pending display list."""
+        if self.on_device():
+            if not callable(spec):
+                self._record(r, spec)
+                return
+            self._to_host()
         b = self._local_box(r)
         if b is None:
             return
         zi, yi, xs = b
-        if pred is None:
+        if spec is None:
             self.dot_mask(zi, yi, xs)
             return
+        pred = spec if callable(spec) else _predicate(spec)
         X, Y, Z = self._coords(zi, yi, xs)
         m = np.broadcast_to(pred(X, Y, Z), (len(zi), len(yi), xs.stop - xs.start))
         if m.any():
             self.dot_mask(zi, yi, xs, np.array(m))
+
+    # ------------------------------------------------------------------ device painting
+    def on_device(self) -> bool:
+        """where this geometry is painted: TCLB_GEOMETRY = auto | host | device, auto being
+        the device when the geometry is drawn for a lattice on a GPU (Geometry.lattice) and
+        the host otherwise.  Decided once, at the first paint or load."""
+        if self.paint_device is None:
+            mode = os.environ.get("TCLB_GEOMETRY") or "auto"
+            if mode not in ("auto", "host", "device"):
+                raise ValueError(f"TCLB_GEOMETRY '{mode}' is none of auto, host, device")
+            lat = self.lattice
+            gpu = lat is not None and lat.device.type == "cuda"
+            if mode == "device" and not gpu:
+                raise ValueError("TCLB_GEOMETRY 'device' needs a lattice on a GPU")
+            self.paint_device = gpu and mode != "host"
+        return self.paint_device
+
+    def _record(self, r: Region, spec):
+        """append the primitive to the display list; flags go up first if the host holds them"""
+        import torch
+        b = r.intersect(self.total)
+        if b.size() == 0:
+            return
+        if self.flags_device is None:
+            dev = self.lattice.device
+            self._rows = tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+                               for a in (self.ys, self.zs))
+        if not self._device_current:
+            self.flags_device = torch.from_numpy(self.flags.view(np.int32)).to(self.lattice.device)
+            self._device_current = True
+        self._batch.append((b, self.fg, self.fg_mask, self.fg_mode, spec or (K_BOX, 0, ())))
+        if len(self._batch) >= self.paint_batch:
+            self._flush()
+
+    def _pack(self) -> np.ndarray:
+        """the pending display list as ops.device.paint_rec() records"""
+        from ..ops import device as D
+        rec = np.zeros(len(self._batch), dtype=D.paint_rec())
+        for q, (b, fg, mask, mode, (kind, opt, p)) in zip(rec, self._batch):
+            q["kind"], q["mode"], q["opt"] = kind, mode, opt
+            q["box"] = (b.dx, b.dx + b.nx, b.dy, b.dy + b.ny, b.dz, b.dz + b.nz)
+            q["fg"], q["mask"] = fg & 0xFFFFFFFF, mask & 0xFFFFFFFF
+            if kind == K_MASK:
+                t, win, q["bit"], q["outside"] = p
+                q["win"], q["ptr"] = win, t.data_ptr()
+                q["sy"], q["sz"] = (t.stride(1), t.stride(0)) if t.numel() else (0, 0)
+            else:
+                q["p"][:len(p)] = p
+        return rec
+
+    def _flush(self):
+        """one k_paint pass over the pending records"""
+        if not self._batch:
+            return
+        import torch
+        from ..ops import device as D
+        lat = self.lattice
+        with torch.cuda.device(lat.device):
+            self.device_paints += D.paint(self.flags_device, self._rows[0], self._rows[1], self._pack(),
+                                          lat._stream())
+        self._batch = []          # and with it the mask tensors the records point into
+
+    def _to_host(self):
+        """flags as the host array, ahead of host painting or at the end of load"""
+        self._flush()
+        if self._device_current:
+            self.flags = self.flags_device.cpu().numpy().view(np.uint32)
+            self._device_current = False
 
     def record_cuts(self, r: Region, cuts: np.ndarray):
         """store STL surface cuts (26, r.nz, r.ny, r.nx) into the local cut array"""
@@ -299,11 +396,9 @@ class Geometry:
             if tag == "Box":
                 self.paint(reg)
             elif tag == "HalfSphere":
-                self.paint(reg, lambda X, Y, Z, r=reg: _in_sphere((.5 + X - r.dx) / r.nx, 0.5 - (.5 + Y - r.dy) / r.ny / 2.,
-                                                                 (.5 + Z - r.dz) / r.nz))
+                self.paint(reg, _sphere(reg, SPH_X | SPH_HALF | SPH_Z))
             elif tag == "Sphere":
-                self.paint(reg, lambda X, Y, Z, r=reg: _in_sphere((.5 + X - r.dx) / r.nx, (.5 + Y - r.dy) / r.ny,
-                                                                 (.5 + Z - r.dz) / r.nz))
+                self.paint(reg, _sphere(reg, SPH_X | SPH_Y | SPH_Z))
             elif tag == "OffgridSphere":
                 x0, y0, z0 = (self._attr_f(n, a) for a in "xyz")
                 if n.get("R") is None:
@@ -312,8 +407,7 @@ class Geometry:
                     Rx = Ry = Rz = self._attr_f(n, "R")
                 r = Region(int(x0 - Rx - 5), int(y0 - Ry - 5), int(z0 - Rz - 5), int(2 * Rx + 10), int(2 * Ry + 10),
                            int(2 * Rz + 10))
-                self.paint(r, lambda X, Y, Z: ((.5 + X - x0) ** 2 / Rx ** 2 + (.5 + Y - y0) ** 2 / Ry ** 2 +
-                                               (.5 + Z - z0) ** 2 / Rz ** 2) < 1.)
+                self.paint(r, _ellipse("xyz", (x0, y0, z0), (Rx ** 2, Ry ** 2, Rz ** 2)))
             elif tag == "OffgridPipe":
                 x0, y0, z0 = (self._attr_f(n, a) for a in "xyz")
                 if n.get("R") is None:
@@ -322,7 +416,7 @@ class Geometry:
                     Rx = Ry = self._attr_f(n, "R")
                 r = reg.copy()
                 r.dx, r.dy, r.nx, r.ny = int(x0 - Rx - 5), int(y0 - Ry - 5), int(2 * Rx + 10), int(2 * Ry + 10)
-                self.paint(r, lambda X, Y, Z: ((.5 + X - x0) ** 2 / Rx ** 2 + (.5 + Y - y0) ** 2 / Ry ** 2) < 1.)
+                self.paint(r, _ellipse("xy", (x0, y0), (Rx ** 2, Ry ** 2)))
             elif tag in ("XPipe", "YPipe", "ZPipe"):
                 self._axis_pipe(n, reg, tag[0])
             elif tag == "XAnnulus":
@@ -334,25 +428,24 @@ class Geometry:
                     Ryi = Rzi = self._attr_f(n, "Ri")
                 r = reg.copy()
                 r.dy, r.dz, r.ny, r.nz = int(y0 - Ryo - 5), int(z0 - Rzo - 5), int(2 * Ryo + 10), int(2 * Rzo + 10)
-                self.paint(r, lambda X, Y, Z: ((.5 + Z - z0) ** 2 / Rzo ** 2 + (.5 + Y - y0) ** 2 / Ryo ** 2 < 1.) &
-                           ((.5 + Z - z0) ** 2 / Rzi ** 2 + (.5 + Y - y0) ** 2 / Ryi ** 2 > 1.))
+                self.paint(r, _ellipse("zy", (z0, y0), (Rzo ** 2, Ryo ** 2), inner=(Rzi ** 2, Ryi ** 2)))
             elif tag == "Pipe":
                 r = Region(reg.dx, reg.dy - 1, reg.dz - 1, reg.nx, reg.ny + 2, reg.nz + 2)
-                self.paint(r, lambda X, Y, Z, q=reg: ~_in_sphere(0.5, (.5 + Y - q.dy) / q.ny, (.5 + Z - q.dz) / q.nz))
+                self.paint(r, _sphere(reg, SPH_Y | SPH_Z | SPH_NOT))
             elif tag == "PipeY":
                 r = Region(reg.dx - 1, reg.dy, reg.dz - 1, reg.nx + 2, reg.ny, reg.nz + 2)
-                self.paint(r, lambda X, Y, Z, q=reg: ~_in_sphere(0.5, (.5 + X - q.dx) / q.nx, (.5 + Z - q.dz) / q.nz))
+                self.paint(r, _sphere(reg, SPH_X | SPH_Z | SPH_NOT))
             elif tag == "PipeZ":
                 r = Region(reg.dx - 1, reg.dy - 1, reg.dz, reg.nx + 2, reg.ny + 2, reg.nz)
-                self.paint(r, lambda X, Y, Z, q=reg: ~_in_sphere(0.5, (.5 + Y - q.dy) / q.ny, (.5 + X - q.dx) / q.nx))
+                self.paint(r, _sphere(reg, SPH_X | SPH_Y | SPH_NOT))
             elif tag == "Cylinder":
                 r = Region(reg.dx, reg.dy - 1, reg.dz - 1, reg.nx, reg.ny + 2, reg.nz + 2)
-                self.paint(r, lambda X, Y, Z, q=reg: _in_sphere((.5 + X - q.dx) / q.nx, (.5 + Y - q.dy) / q.ny, 0.5 + 0 * Z))
+                self.paint(r, _sphere(reg, SPH_X | SPH_Y))
             elif tag == "Wedge":
-                typ = n.get("direction", "")
-                self.paint(reg, lambda X, Y, Z, q=reg: _in_wedge((X - q.dx) / max(q.nx - 1., 1e-300),
-                                                                 (Y - q.dy) / max(q.ny - 1., 1e-300),
-                                                                 (Z - q.dz) / max(q.nz - 1., 1e-300), typ))
+                typ = n.get("direction", "") or "UpperLeft"
+                d = WEDGE_DIRS.index(typ) if typ in WEDGE_DIRS else len(WEDGE_DIRS)
+                self.paint(reg, (K_WEDGE, d, (float(reg.dx), float(reg.dy), float(reg.dz), max(reg.nx - 1., 1e-300),
+                                              max(reg.ny - 1., 1e-300), max(reg.nz - 1., 1e-300))))
             elif tag == "STL":
                 from .stl import draw_stl
                 draw_stl(self, reg, n)
@@ -384,12 +477,12 @@ class Geometry:
         # NB: the reference YPipe/ZPipe use (x - y0) for the x offset (src/Geometry.cpp.Rt:930,969);
         # we keep that quirk for parity of existing cases.
         if ax == "X":
-            pred = lambda X, Y, Z: ((.5 + Z - z0) ** 2 / Rb ** 2 + (.5 + Y - y0) ** 2 / Ra ** 2) < 1.
+            spec = _ellipse("zy", (z0, y0), (Rb ** 2, Ra ** 2))
         elif ax == "Y":
-            pred = lambda X, Y, Z: ((.5 + Z - z0) ** 2 / Rb ** 2 + (.5 + X - y0) ** 2 / Ra ** 2) < 1.
+            spec = _ellipse("zx", (z0, y0), (Rb ** 2, Ra ** 2))
         else:
-            pred = lambda X, Y, Z: ((.5 + Y - y0) ** 2 / Rb ** 2 + (.5 + X - y0) ** 2 / Ra ** 2) < 1.
-        self.paint(r, pred)
+            spec = _ellipse("yx", (y0, y0), (Rb ** 2, Ra ** 2))
+        self.paint(r, spec)
 
     def _sweep(self, reg, node):
         order = int(node.get("order", "1"))
@@ -414,7 +507,8 @@ class Geometry:
                 prev = (x0, y0, z0, r)
                 rr = reg.intersect(Region(int(x0 - r - 1), int(y0 - r - 1), int(z0 - r - 1), int(2 * r + 2),
                                           int(2 * r + 2), int(2 * r + 2)))
-                self.paint(rr, lambda X, Y, Z: (.5 + X - x0) ** 2 + (.5 + Y - y0) ** 2 + (.5 + Z - z0) ** 2 < r * r)
+                # the reference's plain sum of squares: the division by 1. is exact
+                self.paint(rr, _ellipse("xyz", (x0, y0, z0), (1., 1., 1.), lim=r * r))
             l += dl
 
     def _text(self, reg, node):
@@ -456,6 +550,7 @@ class Geometry:
                 node.insert(0, z)
         self._xml = node
         self._parent = {c: p for p in node.iter() for c in p}
+        self.on_device()
         for n in list(node):
             if n.tag in ("Zone", "Type", "Mask"):
                 continue
@@ -474,7 +569,85 @@ class Geometry:
                     raise GeometryError(f"Unknown zone (in xml): {n.get('zone')}")
                 self.draw(z)
             self.draw(n)
+        self._flush()
+        if self._device_current:          # flags_device stays current: device_flags()
+            self.flags = self.flags_device.cpu().numpy().view(np.uint32)
         return self
+
+    def device_flags(self):
+        """the flags as an int32 (NZ, NY, gnx) tensor on the lattice's GPU, if they were
+        painted there and the host array has not been painted since (else None)"""
+        return self.flags_device if self._device_current and not self._batch else None
+
+
+# A primitive is a spec (kind, opt, doubles); the host predicate (_predicate) and the device
+# record (Geometry._pack, csrc/device/paint.hip) are both made from it.
+K_BOX, K_SPHERE, K_ELLIPSE, K_WEDGE, K_MASK = range(5)
+# K_SPHERE opt: the axes that enter _in_sphere (the others sit at the centre, 0.5), the
+# HalfSphere y mapping, negation (the Pipe family paints the outside)
+SPH_X, SPH_Y, SPH_Z, SPH_HALF, SPH_NOT = 1, 2, 4, 8, 16
+# K_ELLIPSE opt: axis of term t (0 x, 1 y, 2 z, 3 none) in bits 2t, 2t + 1; ELL_INNER: an inner
+# ellipse the node has to lie outside of
+ELL_INNER = 64
+WEDGE_DIRS = ["UpperLeft", "UpperRight", "LowerLeft", "LowerRight", "UpperLeftXZ", "UpperRightXZ", "LowerLeftXZ",
+              "LowerRightXZ"]
+
+
+def _sphere(q: Region, opt: int):
+    """_in_sphere of ((.5 + C) - q.d) / q.n per enabled axis: (dx, dy, dz, nx, ny, nz)"""
+    return K_SPHERE, opt, (float(q.dx), float(q.dy), float(q.dz), float(q.nx), float(q.ny), float(q.nz))
+
+
+def _ellipse(axes: str, c, R2, lim: float = 1., inner=None):
+    """sum over the terms of ((.5 + C_axis) - c) ** 2 / R2, in this order, < lim, and with
+    `inner` the same numerators over inner's R2 > 1: (c[3], R2[3], lim, inner[3])"""
+    k = len(axes)
+    opt = sum(("xyz".index(a) if a else 3) << (2 * t) for t, a in enumerate(list(axes) + [""] * (3 - k)))
+    pad = (1.,) * (3 - k)
+    p = tuple(float(v) for v in c) + (0.,) * (3 - k) + tuple(float(v) for v in R2) + pad + (float(lim),)
+    if inner is not None:
+        opt |= ELL_INNER
+        p += tuple(float(v) for v in inner) + pad
+    return K_ELLIPSE, opt, p
+
+
+def _predicate(spec):
+    """the NumPy predicate pred(X, Y, Z) of a spec, the reference's expression term for term"""
+    kind, opt, p = spec
+    if kind == K_SPHERE:
+        dx, dy, dz, nx, ny, nz = p
+
+        def pred(X, Y, Z):
+            x = (.5 + X - dx) / nx if opt & SPH_X else 0.5
+            if opt & SPH_HALF:
+                y = 0.5 - (.5 + Y - dy) / ny / 2.
+            else:
+                y = (.5 + Y - dy) / ny if opt & SPH_Y else 0.5
+            z = (.5 + Z - dz) / nz if opt & SPH_Z else 0.5
+            m = _in_sphere(x, y, z)
+            return ~m if opt & SPH_NOT else m
+    elif kind == K_ELLIPSE:
+        axes = [a for a in ((opt >> (2 * t)) & 3 for t in range(3)) if a != 3]
+
+        def pred(X, Y, Z):
+            sq = [(.5 + (X, Y, Z)[a] - p[t]) ** 2 for t, a in enumerate(axes)]
+            s = sq[0] / p[3]
+            for t in range(1, len(sq)):
+                s = s + sq[t] / p[3 + t]
+            if not opt & ELL_INNER:
+                return s < p[6]
+            si = sq[0] / p[7]
+            for t in range(1, len(sq)):
+                si = si + sq[t] / p[7 + t]
+            return (s < p[6]) & (si > 1.)
+    elif kind == K_WEDGE:
+        typ = WEDGE_DIRS[opt] if opt < len(WEDGE_DIRS) else "?"
+
+        def pred(X, Y, Z):
+            return _in_wedge((X - p[0]) / p[3], (Y - p[1]) / p[4], (Z - p[2]) / p[5], typ)
+    else:
+        raise GeometryError(f"no host predicate for primitive kind {kind}")
+    return pred
 
 
 def _in_sphere(x, y, z):

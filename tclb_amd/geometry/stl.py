@@ -1,7 +1,9 @@
 """STL primitive (reference Geometry::loadSTL / transformSTL, src/Geometry.cpp.Rt:397-688).
 Binary STL only; transforms Xrot/Yrot/Zrot, scale, x/y/z; sides in/out (ray parity) and
 surface (sub-voxel cuts for interpolated bounce-back), both by the native host library or,
-for a lattice on a GPU, by the device kernels of csrc/device/voxel.hip; same bits."""
+for a lattice on a GPU, by the device kernels of csrc/device/voxel.hip; same bits.  Where the
+geometry is painted on the device too (Geometry.on_device), the mask or level bytes stay
+there and enter the display list as a MASK record."""
 from __future__ import annotations
 
 import math
@@ -90,15 +92,18 @@ def draw_stl(geom, reg, node):
     if inside_out == 2 and _surface_on_device(geom):
         import torch
         from ..ops import device
-        from .geometry import Region
+        from .geometry import K_MASK, Region
         lat = geom.lattice
         with torch.cuda.device(lat.device):
             cuts, mask, win = device.stl_cuts(tri, box, D3Q27_DIRS, lat._stream())
             lat.merge_cuts(cuts, win, geom.ys, geom.zs)
+            r = Region(*win)
+            if r.size() == 0:
+                return
+            if geom.on_device():                        # the mask stays on the device
+                geom.paint(r, (K_MASK, 0, (mask, win, 0xFF, 0)))
+                return
             sel = mask.cpu().numpy().astype(bool)       # the window's mask only
-        r = Region(*win)
-        if r.size() == 0:
-            return
     elif inside_out == 2:
         cuts, mask = host.stl_cuts(tri, box, D3Q27_DIRS)
         geom.record_cuts(r, cuts)
@@ -106,13 +111,19 @@ def draw_stl(geom, reg, node):
     elif _on_device(geom):
         import torch
         from ..ops import device
-        from .geometry import Region
+        from .geometry import K_MASK, Region
         lat = geom.lattice
         with torch.cuda.device(lat.device):
             lev, win = device.stl_fill(tri, box, axis, inside_out, lat._stream())
+            lat.stl_fills += 1
+            w = Region(*win)
+            if geom.on_device():                           # the levels stay on the device, bit 0 selects
+                if inside_out == 0 and w.size() == 0:
+                    return
+                # side="out": off the window every node of the region is selected
+                geom.paint(w if inside_out == 0 else r, (K_MASK, 0, (lev, win, 1, inside_out)))
+                return
             odd = (lev.cpu().numpy() & 1).astype(bool)     # the window's levels only
-        lat.stl_fills += 1
-        w = Region(*win)
         if inside_out == 0:
             # outside the window nothing is selected: paint the window alone
             r, sel = w, odd

@@ -114,7 +114,8 @@ class GeometryAction(Action):
         g.lattice = lat      # STL surfaces are voxelised on its GPU, their cuts merged into lat.cuts
         g.load(self.node)
         s.geometry = g
-        lat.set_flags(g.flags)
+        dflags = g.device_flags()       # painted on the GPU: no second upload
+        lat.set_flags(g.flags if dflags is None else dflags)
         for z in g.zones:
             lat.add_zone(z)
         if g.cuts is not None:

@@ -902,9 +902,19 @@ class Lattice:
         return zi
 
     # ------------------------------------------------------------------ flags
-    def set_flags(self, flags: np.ndarray):
-        """flags: (NZ, NY, nx) incl. ghost planes along the decomposed axis"""
+    def set_flags(self, flags):
+        """flags: (NZ, NY, nx) incl. ghost planes along the decomposed axis: a NumPy array, or a
+        uint32 (or int32, same bits) tensor on the lattice's device, padded and narrowed there"""
         nx = self.shape[0]
+        if isinstance(flags, torch.Tensor):
+            if flags.device != self.flags.device or tuple(flags.shape) != (self.NZ, self.NY, nx) or \
+                    flags.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                raise ValueError(f"set_flags: a ({self.NZ}, {self.NY}, {nx}) uint32 tensor on {self.device} expected")
+            self.flags[:, :, nx:].zero_()
+            # int32 -> int16 keeps the low half, as the NumPy form does
+            self.flags[:, :, :nx].copy_(flags.view(torch.int32))
+            self.flags_changed()
+            return
         full = np.zeros((self.NZ, self.NY, self.px), dtype=np.uint16 if self.model.flag_bits == 16 else np.uint32)
         full[:, :, :nx] = flags
         view = full.view(np.int16 if self.model.flag_bits == 16 else np.int32)

@@ -1,6 +1,7 @@
 """ctypes binding of the model-independent HIP runtime kernels (csrc/device/*.hip,
 libtclb_device.so): the per-step particle kernels, the snapshot allocator, the output
-encoders (base64, flag groups) and the STL voxelisers (surface cuts, ray fill).  On a GPU the library must be there
+encoders (base64, flag groups), the STL voxelisers (surface cuts, ray fill) and the geometry
+painter (display list of primitives -> flag array).  On a GPU the library must be there
 (built by ``tclb_amd.build``); a missing or stale one is an error, not a silent switch to
 tensor ops."""
 from __future__ import annotations
@@ -66,6 +67,8 @@ def lib():
             L.tclb_stl_ray_fill.restype = i
             L.tclb_cuts_merge.argtypes = [P, i, i, i, LL, P, LL, i, i, i, i, i, i, P, P, P]
             L.tclb_cuts_merge.restype = i
+            L.tclb_paint.argtypes = [P, i, i, i, P, P, P, i, i, i, i, i, i, i, i, P]
+            L.tclb_paint.restype = i
             _lib = L
     return _lib
 
@@ -287,6 +290,79 @@ def cuts_merge(dst, win, window, ys, zs, stream=None):
         _check(lib().tclb_cuts_merge(dst.data_ptr(), NZ, NY, px, dst.stride(0), win.data_ptr(), win.stride(0),
                                      x0, y0, z0, wx, wy, wz, ys.data_ptr(), zs.data_ptr(), stream),
                "STL cut merge")
+
+
+# one record of a paint display list (csrc/device/paint.hip PaintRec)
+PAINT_BOX, PAINT_SPHERE, PAINT_ELLIPSE, PAINT_WEDGE, PAINT_MASK = range(5)
+PAINT_CHUNK = 4096                  # records of one k_paint launch
+PAINT_REC = None
+
+
+def paint_rec():
+    """numpy dtype of a paint record: kind, mode (0 overwrite, 1 fill, 2 change), box (x0, x1,
+    y0, y1, z0, z1: global, half open, inside the lattice), fg, mask, opt (flags of the kind),
+    for PAINT_MASK bit, outside, win (x0, y0, z0, nx, ny, nz), ptr, sy, sz of the byte window,
+    and the kind's doubles p[10]"""
+    global PAINT_REC
+    if PAINT_REC is None:
+        import numpy as np
+        PAINT_REC = np.dtype([("kind", "<i4"), ("mode", "<i4"), ("box", "<i4", 6), ("fg", "<u4"), ("mask", "<u4"),
+                              ("opt", "<i4"), ("bit", "<i4"), ("outside", "<i4"), ("win", "<i4", 6), ("pad", "<i4"),
+                              ("ptr", "<u8"), ("sy", "<i8"), ("sz", "<i8"), ("p", "<f8", 10)])
+        assert PAINT_REC.itemsize == 184
+    return PAINT_REC
+
+
+def paint(flags, ys, zs, records, stream=None) -> int:
+    """paint the display list `records` (host array of paint_rec(), drawing order) into
+    `flags`, the (NZ, NY, gnx) uint32 (or int32, same bits) device flag array of a Geometry
+    whose local row (k, j) lies at global (ys[j], zs[k]) (int32 device tensors; ghost and
+    periodic-wrap rows repeat coordinates): per node and record in order, inside the box and
+    the predicate and passing the mode, v = (v & ~mask) | fg, bit for bit the NumPy painter
+    (csrc/device/paint.hip k_paint).  The list is uploaded here; a launch takes PAINT_CHUNK
+    records and covers the local rows and x range of their bounding box.  Returns the number
+    of launches: an empty list launches nothing."""
+    import numpy as np
+    import torch
+    if not flags.is_cuda or flags.dim() != 3 or not flags.is_contiguous() or \
+            flags.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+        raise ValueError("paint: flags must be a contiguous (NZ, NY, gnx) uint32 device tensor")
+    NZ, NY, gnx = flags.shape
+    for t, n in ((ys, NY), (zs, NZ)):
+        if t.device != flags.device or t.dtype != torch.int32 or t.shape != (n,) or not t.is_contiguous():
+            raise ValueError("paint: ys / zs must be int32 device tensors of NY / NZ entries")
+    if not isinstance(records, np.ndarray) or records.dtype != paint_rec() or records.ndim != 1:
+        raise ValueError("paint: records must be a 1-D host array of paint_rec()")
+    if len(records) == 0 or flags.numel() == 0:
+        return 0
+    records = np.ascontiguousarray(records)
+    box, kind = records["box"], records["kind"]
+    if (box[:, 0] < 0).any() or (box[:, 1] > gnx).any() or (kind < 0).any() or (kind > PAINT_MASK).any() or \
+            ((kind == PAINT_MASK) & (records["ptr"] == 0) & (records["win"][:, 3:].min(1) > 0)).any():
+        raise ValueError("paint: a record has a box off the x range, an unknown kind or a mask without data")
+    if stream is None:
+        stream = torch.cuda.current_stream(flags.device).cuda_stream
+    ys_h, zs_h = ys.cpu().numpy(), zs.cpu().numpy()
+    rec_d = torch.from_numpy(records.view(np.uint8)).to(flags.device)
+    launches = 0
+    with torch.cuda.device(flags.device):
+        for c in range(0, len(records), PAINT_CHUNK):
+            b = box[c:c + PAINT_CHUNK]
+            b = b[(b[:, 1::2] > b[:, 0::2]).all(1)]
+            if not len(b):
+                continue
+            lo, hi = b[:, 0::2].min(0), b[:, 1::2].max(0)
+            jj = np.nonzero((ys_h >= lo[1]) & (ys_h < hi[1]))[0]
+            kk = np.nonzero((zs_h >= lo[2]) & (zs_h < hi[2]))[0]
+            if not len(jj) or not len(kk):
+                continue
+            n = min(PAINT_CHUNK, len(records) - c)
+            _check(lib().tclb_paint(flags.data_ptr(), NZ, NY, gnx, ys.data_ptr(), zs.data_ptr(),
+                                    rec_d.data_ptr() + c * PAINT_REC.itemsize, n, PAINT_REC.itemsize,
+                                    int(lo[0]), int(hi[0]), int(jj[0]), int(jj[-1]) + 1, int(kk[0]), int(kk[-1]) + 1,
+                                    stream), "geometry paint")
+            launches += 1
+    return launches
 
 
 SNAP_ALLOC_MODES = {"torch": -1, "hip": 0, "contiguous": 1, "vmm": 2}
