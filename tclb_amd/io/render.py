@@ -11,6 +11,7 @@ is ``Lattice.draw_wall``.
 """
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import numpy as np
@@ -74,8 +75,28 @@ def frame(lat, z: Optional[int] = None) -> Optional[np.ndarray]:
     return out[::-1].copy()
 
 
-def write_png(lat, path: str, z: Optional[int] = None) -> Optional[np.ndarray]:
-    """write the colour frame of slice z to `path` (root rank); returns the image"""
+def write_png(lat, path: str, z: Optional[int] = None, encode: str = "auto") -> Optional[np.ndarray]:
+    """write the colour frame of slice z to `path` (root rank); returns the image.
+    encode: where the file is made — "host" (frame() and the native writer: filter 0, zlib
+    level 6) or "device" (ops.device.png_encode: colour map, Sub filter, run-length deflate
+    and checksums in HIP kernels, the host only writes the finished bytes; a lattice on a
+    GPU and a single rank).  Both decode to the same pixels, the file bytes differ.  "auto"
+    is still the host path everywhere: tests/test_graphics.py reads a frame's rows as
+    stored, without undoing a filter, so the default file keeps filter 0 (profiles/README.md,
+    "Device PNG frames").  The environment's TCLB_PNG_ENCODE overrides the argument."""
+    encode = os.environ.get("TCLB_PNG_ENCODE") or encode
+    if encode not in ("auto", "host", "device"):
+        raise ValueError(f"PNG encode '{encode}' is none of auto, host, device")
+    if encode == "device":
+        if not lat.is_gpu or lat.comm.size > 1:
+            raise ValueError("PNG encode 'device' needs a lattice on a GPU and a single rank")
+        from ..ops.device import png_encode
+        lw = lat.color(z).permute(2, 0, 1).contiguous()        # the (2, ny, nx) planes Lattice.color filled
+        pix = torch.empty((lw.shape[1], lw.shape[2], 4), dtype=torch.uint8, device=lw.device)
+        data = png_encode(lw, pixels=pix)
+        with open(path, "wb") as f:
+            f.write(data.cpu().numpy().data)
+        return pix.cpu().numpy()
     from ..ops.host import png_write
     img = frame(lat, z)
     if img is not None:

@@ -1,6 +1,6 @@
 """ctypes binding of the model-independent HIP runtime kernels (csrc/device/*.hip,
 libtclb_device.so): the per-step particle kernels, the snapshot allocator, the output
-encoders (base64, flag groups), the STL voxelisers (surface cuts, ray fill) and the geometry
+encoders (base64, flag groups, PNG frames), the STL voxelisers (surface cuts, ray fill) and the geometry
 painter (display list of primitives -> flag array).  On a GPU the library must be there
 (built by ``tclb_amd.build``); a missing or stale one is an error, not a silent switch to
 tensor ops."""
@@ -55,6 +55,10 @@ def lib():
                                                ctypes.POINTER(P), P]
             L.tclb_enc_flag_groups.restype = i
             LL = ctypes.c_longlong
+            L.tclb_enc_png_bytes.argtypes = [i, i, ctypes.POINTER(LL), ctypes.POINTER(LL)]
+            L.tclb_enc_png_bytes.restype = i
+            L.tclb_enc_png.argtypes = [P, i, i, i, P, LL, P, LL, P, P, P]
+            L.tclb_enc_png.restype = i
             L.tclb_stl_tmp_bytes.argtypes = [i]
             L.tclb_stl_tmp_bytes.restype = LL
             L.tclb_stl_prep.argtypes = [P, i, i, i, i, i, i, i, P, LL, ctypes.POINTER(LL), P]
@@ -148,6 +152,44 @@ def flag_groups(flags, pairs, stream=None):
                                               flags.stride(1), flags.stride(0), wx, wy, wz, len(part), masks,
                                               shifts, outs, stream), "flag group extraction")
     return [buf[j, :total].view(wz, wy, wx) for j in range(len(pairs))]
+
+
+def png_encode(lw, stream=None, pixels=None):
+    """the colour frame of the (2, ny, nx) colour pair `lw` (l plane, w plane: a contiguous
+    fp32 or fp64 device tensor, as Lattice.color lays it out) as a complete PNG file in one
+    uint8 device tensor: RGBA, 8 bits, image row r = lattice row ny-1-r, the pixels of
+    render.colormap bit for bit (csrc/device/encode.hip k_frame_rows, k_png_pack,
+    k_png_finish).  pixels: an (ny, nx, 4) contiguous uint8 tensor on lw's device that
+    receives the image as well.  stream: a raw HIP stream, default the current one of lw's
+    device; the call waits for it, since the file's length is a result."""
+    import torch
+    if not lw.is_cuda or not lw.is_contiguous() or lw.dim() != 3 or lw.shape[0] != 2 or \
+            lw.dtype not in (torch.float32, torch.float64):
+        raise ValueError("png_encode: lw must be a contiguous (2, ny, nx) fp32 or fp64 device tensor")
+    _, ny, nx = lw.shape
+    if nx <= 0 or ny <= 0 or nx * ny * 4 + ny >= 2 ** 31:
+        raise ValueError(f"png_encode: a frame of {nx} x {ny} is empty or beyond 2^31 bytes")
+    if pixels is not None and (pixels.dtype != torch.uint8 or pixels.device != lw.device or
+                               tuple(pixels.shape) != (ny, nx, 4) or not pixels.is_contiguous()):
+        raise ValueError(f"png_encode: pixels must be a contiguous ({ny}, {nx}, 4) uint8 tensor on {lw.device}")
+    L = lib()
+    nout, ntmp = ctypes.c_longlong(0), ctypes.c_longlong(0)
+    _check(L.tclb_enc_png_bytes(nx, ny, ctypes.byref(nout), ctypes.byref(ntmp)), "PNG frame sizes")
+    out = torch.empty(nout.value, dtype=torch.uint8, device=lw.device)
+    tmp = torch.empty(ntmp.value, dtype=torch.uint8, device=lw.device)
+    count = torch.empty(1, dtype=torch.int64, device=lw.device)
+    if stream is None:
+        stream = torch.cuda.current_stream(lw.device).cuda_stream
+    with torch.cuda.device(lw.device):
+        _check(L.tclb_enc_png(lw.data_ptr(), lw.element_size(), nx, ny, out.data_ptr(), out.numel(), tmp.data_ptr(),
+                              tmp.numel(), 0 if pixels is None else pixels.data_ptr(), count.data_ptr(), stream),
+               "PNG frame encoding")
+        if stream != torch.cuda.current_stream(lw.device).cuda_stream:
+            torch.cuda.ExternalStream(stream, device=lw.device).synchronize()
+    n = int(count.item())
+    if n < 0:
+        raise DeviceRuntimeError(f"png_encode: a frame of {nx} x {ny} does not fit one IDAT chunk")
+    return out[:n]
 
 
 def _stl_box(tri, region, what: str):
